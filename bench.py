@@ -13,8 +13,7 @@ reference's rndrdImg.pixels holds) and send them to rank 0 over RCCL (grouped nc
 each rank's pixels over its own xGMI link), rank 0 scatters them into the frame; frame i's exchange
 overlaps frame i+1's render and the last one is drained inside the timed region (--backend gloo:
 the same native rank mode over the host transport, ranks sharing GPUs -- a rehearsal, not a scaling
-measurement). After timing, rank 0 checks the assembled frame against rt_render bit for bit
-(frame_check). Work per step is one frame whatever N is
+measurement). Work per step is one frame whatever N is
 (strong scaling). value = traced rays of the frame (camera + shadow + reflection + refraction,
 counted exactly by an instrumented run before timing) / max-over-ranks step time.
 
@@ -33,9 +32,17 @@ assumed 4 cycles per instruction; valu_measured: the same from MEASURED issue co
 class (tools/valu_issue.hip x the PMC class counts, tools/valu_model.py) -- the bound this branchy
 fp64 traversal runs into.
 
+A plain run does what the headline figure needs and no more: scene load, photon pre-pass, the
+group, the exact ray count, warm-up, the timed steps, the result line (with the wave-level roofline,
+which costs no run of its own). --dump-outputs DIR writes the frame the last timed step left on rank 0
+(dump_outputs). --full adds, after timing, what takes runs of its own:
+
+frame_check: rank 0 checks the assembled frame against rt_render bit for bit.
+host_path_ms_per_step / host_build_s: the blocking rt_render into host memory, the host-only scene build.
+roofline's 8(d) per-lane figures of the reference algorithm's work (an instrumented RT_RENDER_NOCULL run).
 cpu_baseline: the oracle (CPU restatement of the reference path, fp64) timed on
 the box's CPU share (affinity / cgroup quota / OMP_NUM_THREADS; the host's CPU count and model
-are recorded beside it) on the same frame (rank 0, N=1 only).
+are recorded beside it) on the same frame (rank 0, N=1 only; --no-cpu-baseline leaves it out).
 """
 from __future__ import annotations
 
@@ -224,6 +231,55 @@ def cpu_baseline(cli, W, H, spp, seed, tex, row_step=1):
     }
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000  # --dump-outputs writes at most this much in all
+
+
+class _DeviceInts:
+    """int32 device memory at a raw pointer as torch sees it (the CUDA array interface)."""
+
+    def __init__(self, ptr: int, shape):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<i4", "data": (int(ptr), False),
+                                         "strides": None, "version": 2}
+
+
+def device_frame_to_host(ptr: int, H: int, W: int, dev: int):
+    """The [H, W] int32 ARGB frame at a device pointer (rt_group_frame), copied to host memory."""
+    import torch
+
+    return torch.as_tensor(_DeviceInts(ptr, (H, W)), device=torch.device("cuda", dev)).cpu().numpy().copy()
+
+
+def dump_outputs(out_dir, argb) -> dict:
+    """--dump-outputs: the [H, W] int32 ARGB frame of the last timed step (the reference's
+    rndrdImg.pixels, what the step's caller finds in rank 0's frame buffer) as
+      argb.npy  float64 [H, W]     the packed ints (0xAARRGGBB as signed 32-bit), exact in float64
+      rgb.npy   float32 [H, W, 3]  their R, G, B bytes, 0..255
+    If the two would exceed DUMP_BUDGET_BYTES, the same fixed, seeded sample of pixels of both
+    (argb.npy [n], rgb.npy [n, 3], pixel_index.npy [n] = row * W + column, ascending)."""
+    import numpy as np
+
+    from distraytracer_old_amd import rt
+
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    argb = np.ascontiguousarray(argb, dtype=np.int32)
+    H, W = argb.shape
+    per_pixel = 8 + 3 * 4
+    arrays = {}
+    if H * W * per_pixel > DUMP_BUDGET_BYTES:
+        n = DUMP_BUDGET_BYTES // (per_pixel + 8)
+        idx = np.sort(np.random.default_rng(0x5EED).choice(H * W, size=n, replace=False))
+        arrays["pixel_index"] = idx.astype(np.float64)
+        argb = argb.reshape(-1)[idx]
+    arrays["argb"] = argb.astype(np.float64)
+    arrays["rgb"] = rt.argb_to_rgb8(argb).astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BUDGET_BYTES, total
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+    return {"dir": str(out_dir), "arrays": {k: [str(a.dtype), list(a.shape)] for k, a in arrays.items()}, "bytes": total}
+
+
 def visible_gpus() -> int:
     """GPUs this process may use, counted without initialising HIP (a process that has initialised
     the GPU must not start the ranks): the *_VISIBLE_DEVICES lists, else the KFD topology's GPU
@@ -268,7 +324,13 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="C3")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what takes runs of its own: the frame check against rt_render, "
+                         "the host path's time, the host-only scene build time, the reference algorithm's per-lane byte "
+                         "count (RT_RENDER_NOCULL) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame the last timed step produced as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--partition", default="tiles", choices=["tiles", "bands"],
                     help="N > 1: cost-balanced wave tiles (default) or interleaved 8-row bands")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -314,9 +376,11 @@ def main():
     tex = scenes.prepare(cli)
     # host-side parse + flatten + BVH build alone (rt_scene_inspect_cli: no device), then the full
     # scene load (the same host build + upload to HBM); both outside the scaling metric
-    t = time.perf_counter()
-    rt.inspect_cli(cli, textures=tex)
-    host_build_s = time.perf_counter() - t
+    host_build_s = None
+    if args.full:
+        t = time.perf_counter()
+        rt.inspect_cli(cli, textures=tex)
+        host_build_s = time.perf_counter() - t
     t = time.perf_counter()
     scene = rt.Scene.load_cli(cli, textures=tex, device=dev)
     scene_load_s = time.perf_counter() - t
@@ -402,16 +466,20 @@ def main():
     # runs (top-level culling on: the record loads it issues) and the reference algorithm's work
     # (RT_RENDER_NOCULL: every objList entry tested for every ray, SURVEY 8(d)'s per-ray bytes).
     # A rank's split tiles are counted as tile waves (their samples and rays are the same).
+    # The headline needs the first (the frame's traced rays); the second is a run of its own: --full.
     p_nocull = rt.params(W, H, spp=spp, seed=seed, flags=rt.RENDER_NOCULL)
+    zero = dict.fromkeys(rt.ST_NAMES, 0)
+    sr = zero
     if my_tiles is not None:
-        zero = dict.fromkeys(rt.ST_NAMES, 0)
         st = scene.render_tiles_count(p_frame, my_tiles) if len(my_tiles) else zero
-        sr = scene.render_tiles_count(p_nocull, my_tiles) if len(my_tiles) else zero
+        if args.full:
+            sr = scene.render_tiles_count(p_nocull, my_tiles) if len(my_tiles) else zero
     else:
         r0, r1, rstep, band = rr.rows
         _, _, st = scene.render_count(W, H, spp=spp, seed=seed, rows=(r0, r1), row_step=rstep, row_band=band)
-        _, _, sr = scene.render_count(W, H, spp=spp, seed=seed, rows=(r0, r1), row_step=rstep, row_band=band,
-                                      flags=rt.RENDER_NOCULL)
+        if args.full:
+            _, _, sr = scene.render_count(W, H, spp=spp, seed=seed, rows=(r0, r1), row_step=rstep, row_band=band,
+                                          flags=rt.RENDER_NOCULL)
     counts = torch.tensor([traced_rays(st), algorithmic_bytes(sr), st["camera"], wave_bytes(st), algorithmic_bytes(st)],
                           dtype=torch.float64, device=coll_dev)
     if dist:
@@ -449,7 +517,7 @@ def main():
     t0 = time.perf_counter()
     for i in range(args.steps):
         step(evs[i])
-    drain()  # the last frame's exchange + scatter are inside the timed region
+    last = drain()  # the last frame's exchange + scatter are inside the timed region
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
@@ -461,10 +529,20 @@ def main():
     else:
         kern_ms = sum(a.elapsed_time(b) for a, b in evs) / args.steps
 
-    # the frame the timed steps produced, checked (after timing): rank 0's assembled ARGB frame against
+    # --dump-outputs: the ARGB frame the last timed step left with its caller, read back as it is (no
+    # further render): rank 0's frame buffer of the group (rt_group_frame), or the frame finish() returned
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        if native:
+            last_argb = device_frame_to_host(grp.frame()[1], H, W, dev)
+        else:
+            last_argb = last[1].cpu().numpy().reshape(H, W)
+        dumped = dump_outputs(args.dump_outputs, last_argb)
+
+    # --full: the frame the timed steps produced, checked (after timing): rank 0's assembled ARGB frame against
     # rt_render of the whole frame on rank 0's GPU, bit for bit (every rank takes part in the frame)
     frame_check = None
-    if native:
+    if native and args.full:
         _, got = grp.render_host(W, H, rgb=False)
         if rank == 0:
             want = np.zeros((H, W), dtype=np.int32)
@@ -478,7 +556,7 @@ def main():
     # buffer -- what the JNI draw() does: launch + the 4 B/pixel read-back to
     # pageable host memory, blocking. Timed apart from the steps, after them.
     host_ms = None
-    if world == 1:
+    if world == 1 and args.full:
         px = np.zeros((H, W), dtype=np.int32)
         for _ in range(2):  # this layout's tile-schedule calibration (probe order, then measured order)
             scene.render_argb_into(px, W, H, spp=spp, seed=seed)
@@ -497,7 +575,7 @@ def main():
     if rank == 0:
         # rank-0 kernel: its own algorithmic bytes over its own mean kernel duration
         achieved = my_wbytes / (kern_ms / 1e3) / 1e9
-        achieved_lane = my_bytes / (kern_ms / 1e3) / 1e9
+        achieved_lane = my_bytes / (kern_ms / 1e3) / 1e9 if args.full else None
         achieved_lane_x = my_xbytes / (kern_ms / 1e3) / 1e9
         workload = f"{args.config} {cli} {W}x{H} {spp}spp"
         var_t, var_c = scene.variant()  # the timed and counted render_kernel<CNT, F> instances (same F)
@@ -549,6 +627,7 @@ def main():
             "vs_baseline": None,
             "dtype": "f64",
             "build_id": bid,
+            "full": args.full,
             "data": ("synthetic: bun69k = deterministic subdivision of data/bun500.cli (69,451 tris); "
                      "scene data/p3_t09.cli without the wood line") if args.config == "C3" else
                     f"scene scenes/{cli} (SURVEY 8(d) {args.config}); synthetic inputs where the reference's are missing",
@@ -591,8 +670,8 @@ def main():
                          # the lanes consume, mostly served by the scalar cache / L2 (a wave loads a
                          # record once for all its lanes) -- a rate, not a fraction of HBM peak
                          "cache_served_gbps_8d_per_lane": achieved_lane,
-                         "bytes_per_launch_8d_per_lane": my_bytes,
-                         "bytes_per_ray_8d_per_lane": bytes_frame / max(1.0, rays_frame),
+                         "bytes_per_launch_8d_per_lane": my_bytes if args.full else None,
+                         "bytes_per_ray_8d_per_lane": bytes_frame / max(1.0, rays_frame) if args.full else None,
                          # ... and the same per-lane accounting of the work the kernel does (culling on)
                          "cache_served_gbps_8d_per_lane_executed": achieved_lane_x,
                          "bytes_per_ray_8d_per_lane_executed": xbytes_frame / max(1.0, rays_frame),
@@ -600,7 +679,9 @@ def main():
         }
         if world > 1 and args.backend == "gloo":
             out["rehearsal"] = f"gloo backend, {world} ranks on {ndev} GPU(s): not a scaling measurement"
-        if world == 1 and not args.no_cpu_baseline:
+        if dumped:
+            out["dumped_outputs"] = dumped
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cb = cpu_baseline(cli, W, H, spp, seed, tex)
             cb["frame_s_1thread_extrapolated"] = rays_frame / (cb["value_1thread"] * 1e6)
             out["cpu_baseline"] = cb

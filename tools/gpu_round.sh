@@ -20,9 +20,9 @@ if [ "$PART" = 1 ] || [ "$PART" = all ]; then
 fi
 if [ $rc -eq 0 ] && { [ "$PART" = 2 ] || [ "$PART" = all ]; }; then
   for c in c3 c4 c5; do [ -f $OUT/$c/pmc.json ] && cp $OUT/$c/pmc.json profiles/${TAG}_${c}_pmc.json; done
-  timeout -k 10 600 python3 bench.py --steps 20 --warmup 3 > $OUT/bench_c3.json 2> $OUT/bench_c3.err && \
-  timeout -k 10 300 python3 bench.py --config C4 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_c4.json 2> $OUT/bench_c4.err && \
-  timeout -k 10 300 python3 bench.py --config C5 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_c5.json 2> $OUT/bench_c5.err || rc=$?
+  timeout -k 10 600 python3 bench.py --full --steps 20 --warmup 3 > $OUT/bench_c3.json 2> $OUT/bench_c3.err && \
+  timeout -k 10 300 python3 bench.py --full --config C4 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_c4.json 2> $OUT/bench_c4.err && \
+  timeout -k 10 300 python3 bench.py --full --config C5 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_c5.json 2> $OUT/bench_c5.err || rc=$?
 fi
 echo "chain exit $rc" >> $OUT/status.txt
 exit $rc

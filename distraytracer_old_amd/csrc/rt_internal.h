@@ -91,6 +91,13 @@ int check_photon_params(const HostScene& h);
 int shoot_photons(rt_scene* s, uint64_t seed, int64_t first, int64_t count, std::vector<double>& pos,
                   std::vector<double>& pwr, std::vector<int64_t>& perLight);
 int set_photon_map(rt_scene* s, std::vector<double>& pos, std::vector<double>& pwr);
+// trace.hip, for query.hip's ray queries: the feature mask of the render variant a scene runs and
+// the scene view of a launch (both as rt_render's, by the RT_RENDER_* flags)
+uint32_t render_variant_mask(const rt_scene* s, uint32_t render_flags);
+SceneD render_scene_view(const rt_scene* s, uint32_t render_flags);
+// query.hip: the chunk size of rt_trace_rays (scene creation), its buffers freed (rt_scene_destroy)
+void trace_init(rt_scene* s);
+void trace_free(rt_scene* s);
 // group.hip: the deterministic rank plan (rt_rank_plan)
 void plan_ranks(const uint32_t* cost, int n, int world, double heavy, int slots, int32_t* owner, int32_t* order,
                 const double* weight = nullptr);
@@ -142,4 +149,10 @@ struct rt_scene {
   void* smpTr = nullptr;
   size_t smpCap = 0;  // samples
   size_t wfCap[WF_N] = {};
+  // rt_trace_rays (query.hip): device rays / hits / occlusion bytes of one chunk and their pinned
+  // staging (grow-only), and the chunk size in rays (DISTRAYTRACER_TRACE_CHUNK, read at creation)
+  void* traceDev = nullptr;
+  void* traceStage = nullptr;
+  size_t traceCap = 0;  // rays
+  int64_t traceChunk = 0;
 };

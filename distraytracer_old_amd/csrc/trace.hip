@@ -388,6 +388,7 @@ int rt_scene_create(const rt_scene_desc* desc, int device, rt_scene** out) {
   if (device < 0 || device >= n) return set_error(RT_E_INVALID, "device ordinal out of range");
   rt_scene* s = new rt_scene();
   s->device = device;
+  trace_init(s);
   int rc = build_host_scene(desc, s->hs);
   if (rc == RT_OK) {
     hipError_t e = hipSetDevice(device);
@@ -427,7 +428,8 @@ int rt_scene_photons(const rt_scene* s, double* pos, double* pwr, int64_t n, int
 
 void rt_scene_destroy(rt_scene* s) {
   if (!s) return;
-  if (!s->allocs.empty() || s->stream || s->outRgb || s->outArgb || !s->tileLists.empty() || s->stage || s->wf[rt_scene::WF_CNT] || s->smpCol) {
+  if (!s->allocs.empty() || s->stream || s->outRgb || s->outArgb || !s->tileLists.empty() || s->stage || s->wf[rt_scene::WF_CNT] || s->smpCol ||
+      s->traceDev || s->traceStage) {
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize((hipStream_t)s->stream);
     for (void* p : s->allocs) (void)hipFree(p);
@@ -439,6 +441,7 @@ void rt_scene_destroy(rt_scene* s) {
     for (void* p : s->wf) (void)hipFree(p);
     (void)hipFree(s->smpCol);
     (void)hipFree(s->smpTr);
+    trace_free(s);
     if (s->stage) (void)hipHostFree(s->stage);
     if (s->stream) (void)hipStreamDestroy((hipStream_t)s->stream);
   }
@@ -820,6 +823,9 @@ static SceneD launch_scene(const rt_scene* s, uint32_t flags) {
   if (flags & RT_RENDER_NOCULL) { sd.topBound = s->noCullBound; sd.fastSlab &= ~(SCENE_NEAREST_FIRST | SCENE_WAVE_CULL); }
   return sd;
 }
+
+uint32_t rt::render_variant_mask(const rt_scene* s, uint32_t render_flags) { return variant_mask(s->hs, render_flags); }
+SceneD rt::render_scene_view(const rt_scene* s, uint32_t render_flags) { return launch_scene(s, render_flags); }
 
 // tiles: an explicit tile list (rt_render_tiles_device) -- ntiles blocks, block b renders tiles[b]
 static int launch(rt_scene* s, const ParamsD& P0, uint32_t flags, float* d_rgb, int32_t* d_argb, bool count,

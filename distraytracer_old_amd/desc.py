@@ -78,9 +78,32 @@ class SceneDesc(ctypes.Structure):
                 ("instances", ctypes.POINTER(InstanceDesc))]
 
 
+class Ray(ctypes.Structure):
+    """rt_ray: a caller ray of rt_trace_rays (tmax: occlusion only)."""
+    _fields_ = [("o", D3), ("d", D3), ("tmax", ctypes.c_double)]
+
+
+class Hit(ctypes.Structure):
+    """rt_hit: a closest-hit record of rt_trace_rays."""
+    _fields_ = [("t", ctypes.c_double), ("pos", D3), ("normal", D3), ("prim", ctypes.c_int32), ("top", ctypes.c_int32),
+                ("material", ctypes.c_int32), ("args", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("pad", ctypes.c_int32)]
+
+
+class TraceParams(ctypes.Structure):
+    _fields_ = [("seed", ctypes.c_uint64), ("first_key", ctypes.c_uint64), ("flags", ctypes.c_uint32),
+                ("pad", ctypes.c_uint32)]
+
+
+# the numpy views of rt_ray / rt_hit arrays (same layout as the ctypes mirrors)
+RAY_DTYPE = np.dtype([("o", "<f8", 3), ("d", "<f8", 3), ("tmax", "<f8")])
+HIT_DTYPE = np.dtype([("t", "<f8"), ("pos", "<f8", 3), ("normal", "<f8", 3), ("prim", "<i4"), ("top", "<i4"),
+                      ("material", "<i4"), ("args", "<i4"), ("flags", "<u4"), ("pad", "<i4")])
+assert RAY_DTYPE.itemsize == ctypes.sizeof(Ray) == 56 and HIT_DTYPE.itemsize == ctypes.sizeof(Hit) == 80
+
 STRUCTS = {"rt_prim_desc": PrimDesc, "rt_material_desc": MaterialDesc, "rt_light_desc": LightDesc,
            "rt_accel_desc": AccelDesc, "rt_instance_desc": InstanceDesc, "rt_texture_desc": TextureDesc,
-           "rt_scene_desc": SceneDesc}
+           "rt_scene_desc": SceneDesc, "rt_ray": Ray, "rt_hit": Hit, "rt_trace_params": TraceParams}
 
 
 class SceneBuilder:

@@ -58,7 +58,9 @@ EXPORTS = ["rt_abi_version", "rt_build_id", "rt_last_error", "rt_device_count", 
            # ABI 7: communicators (RCCL / caller host transport), the group and the photon pre-pass over them
            "rt_comm_create_rccl", "rt_comm_create_host", "rt_comm_info", "rt_comm_destroy", "rt_comm_selftest",
            "rt_group_create_comm",
-           "rt_photons_build_comm", "rt_photons_build_local"]
+           "rt_photons_build_comm", "rt_photons_build_local",
+           # added to ABI 7: ray queries (closest hit / occlusion of caller rays)
+           "rt_trace_rays", "rt_trace_rays_device"]
 
 _lib = None
 
@@ -165,6 +167,10 @@ def lib():
                                                ctypes.POINTER(vp)]
             L.rt_photons_build_comm.argtypes = [vp, vp, ctypes.c_uint64]
             L.rt_photons_build_local.argtypes = [vp, i32, ctypes.c_uint64]
+        if hasattr(L, "rt_trace_rays"):  # added to ABI 7
+            vp, i64 = ctypes.c_void_p, ctypes.c_int64
+            L.rt_trace_rays.argtypes = [vp, vp, vp, i64, vp, vp]
+            L.rt_trace_rays_device.argtypes = [vp, vp, vp, i64, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -529,6 +535,25 @@ RENDER_WAVEFRONT = 32  # RT_RENDER_WAVEFRONT: level-synchronous shading (same im
 RENDER_PIXEL_WAVES = 64  # RT_RENDER_PIXEL_WAVES: one pixel per wave (same image)
 
 
+TRACE_ANY = 1  # RT_TRACE_ANY: occlusion (calcShadow) instead of the closest hit
+TRACE_LANES = 2  # RT_TRACE_LANES: per-lane reference-order traversal, all fp64
+TRACE_NOCULL = 4  # RT_TRACE_NOCULL: no bounding-sphere cull, no nearest-first order
+TRACE_GENERIC = 8  # RT_TRACE_GENERIC: the all-features instantiation
+HIT_HIT, HIT_INSTANCE, HIT_IN_ACCEL, HIT_BAD_RAY = 1, 2, 4, 8  # RT_HIT_*
+
+
+def rays(o, d, tmax=np.inf) -> np.ndarray:
+    """rt_ray array (desc.RAY_DTYPE) of origins o [n, 3], directions d [n, 3] and tmax (scalar or [n])."""
+    from .desc import RAY_DTYPE
+
+    o = np.asarray(o, dtype=np.float64).reshape(-1, 3)
+    r = np.zeros(len(o), dtype=RAY_DTYPE)
+    r["o"] = o
+    r["d"] = np.asarray(d, dtype=np.float64).reshape(-1, 3)
+    r["tmax"] = tmax
+    return r
+
+
 def params(W, H, spp=0, seed=0x5EED0001, rows=None, row_step=1, flags=0, row_band=1) -> RenderParams:
     r0, r1 = (0, H) if rows is None else rows
     return RenderParams(W, H, spp, r0, r1, row_step, seed, flags, row_band)
@@ -696,6 +721,41 @@ class Scene:
         out = np.zeros_like(pts)
         _check(lib().rt_photon_gather(self._h, pts.ctypes.data, out.ctypes.data, len(pts)), "rt_photon_gather")
         return out
+
+    def trace(self, o, d, seed=0, first_key=0, flags=0) -> np.ndarray:
+        """Closest hits of the rays (o [n, 3], d [n, 3]) -> structured array (desc.HIT_DTYPE) [n]
+        (rt_trace_rays; flags: TRACE_LANES / TRACE_NOCULL / TRACE_GENERIC)."""
+        from .desc import HIT_DTYPE, TraceParams
+
+        r = rays(o, d)
+        hits = np.zeros(len(r), dtype=HIT_DTYPE)
+        p = TraceParams(seed, first_key, flags & ~TRACE_ANY, 0)
+        _check(lib().rt_trace_rays(self._h, ctypes.byref(p), r.ctypes.data, len(r), hits.ctypes.data, None),
+               "rt_trace_rays")
+        return hits
+
+    def occluded(self, o, d, tmax, seed=0, first_key=0, flags=0) -> np.ndarray:
+        """calcShadow of the rays with dist = tmax (scalar or [n]; inf allowed) -> uint8 [n]: 1 blocked,
+        0 free, 2 rejected ray (rt_trace_rays with RT_TRACE_ANY)."""
+        from .desc import TraceParams
+
+        r = rays(o, d, tmax)
+        occ = np.zeros(len(r), dtype=np.uint8)
+        p = TraceParams(seed, first_key, flags | TRACE_ANY, 0)
+        _check(lib().rt_trace_rays(self._h, ctypes.byref(p), r.ctypes.data, len(r), None, occ.ctypes.data),
+               "rt_trace_rays")
+        return occ
+
+    def trace_device(self, rays_ptr: int, n: int, hits_ptr: int = 0, occ_ptr: int = 0, stream: int = 0, seed=0,
+                     first_key=0, flags=0):
+        """Asynchronous trace of n device rt_ray (e.g. torch tensors' data_ptr()) into device rt_hit
+        (closest hit) or uint8 (flags & TRACE_ANY) buffers on a HIP stream (rt_trace_rays_device)."""
+        from .desc import TraceParams
+
+        p = TraceParams(seed, first_key, flags, 0)
+        _check(lib().rt_trace_rays_device(self._h, ctypes.byref(p), ctypes.c_void_p(rays_ptr or None), n,
+                                          ctypes.c_void_p(hits_ptr or None), ctypes.c_void_p(occ_ptr or None),
+                                          ctypes.c_void_p(stream or None)), "rt_trace_rays_device")
 
     def render_pixels_device(self, p: RenderParams, pixels: np.ndarray, rgb_ptr: int, argb_ptr: int, stream: int = 0):
         """Asynchronous one-sample-per-wave render of the listed pixels (host int32 list) into whole-frame buffers."""

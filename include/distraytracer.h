@@ -461,6 +461,65 @@ int rt_photon_kdtree(const double* pos, int64_t n, int32_t* out);
    the photon map's leaf-ordered arrays (rt_scene_photon_map ppos / ppwr), axis, left, right}. */
 int rt_scene_photon_kdtree(const rt_scene* scene, int32_t* out, int64_t n);
 
+/* ---- Ray queries (added to ABI 7; probe with dlsym) -------------------------------------------------
+   The caller's own rays through the render kernels' intersection code: closest hit
+   (myScene.findClosestRayHit, myScene.java:888-903) or occlusion (myScene.calcShadow, :879-885).
+   RT_ABI_VERSION stays 7: a host that may meet an older ABI-7 library looks the two entries up with
+   dlsym before calling them.
+
+   Ray i is built as the myRay constructor builds it: d normalised once, no re-normalisation applied yet.
+   A ray with a non-finite component of o or d, a zero d or a NaN tmax is rejected: it is reported as a
+   miss (RT_HIT_BAD_RAY; occluded 2) and never traversed.
+
+   Closest hit writes hits[n]: t is the reference's hit parameter (the one findClosestRayHit compares,
+   in the winning object's space), pos the world hit location (fwdTransHitLoc), normal the world normal,
+   args the primitive's hit argument (planar orientation, cylinder face, box plane), prim the index
+   into rt_scene_desc.prims (creation order; for a hit through an instance, the base primitive), top the
+   objList index, material the shader index. tmax is ignored: the reference's closest hit has no bound.
+
+   Occlusion (RT_TRACE_ANY) writes occluded[n]: 1 iff an objList entry reports a hit with
+   tmax - t > 1e-7 (calcShadow's rule with dist = tmax; +Inf is allowed), 0 free, 2 rejected.
+
+   Moving spheres draw their ray time from the key {seed, pixel = first_key + i, sample 0, node 1}
+   (camera-ray site for closest hits, shadow-ray site for occlusion): seed 0 and row-major camera rays
+   reproduce an un-jittered 1-spp frame's keys.
+
+   RT_TRACE_LANES traverses every BVH lane by lane in the reference's order, in fp64 throughout; the
+   default walks a wave's 64 rays as one packet with the render kernel's fp32 pre-tests and nearest-first
+   order. Both return the same records; which is faster depends on how coherent a batch is.
+   The kernel is the instantiation for the feature mask the scene's render runs (rt_render_variant) where
+   one of {none, C4's, C5's, all} matches exactly, else the all-features one (also RT_TRACE_GENERIC).
+
+   rt_trace_rays: host buffers, blocking, on the scene's own stream, staged in chunks through grow-only
+   buffers the scene owns. rt_trace_rays_device: device buffers, asynchronous on hip_stream. n == 0 is
+   RT_OK. Neither builds photons. A trace counts as the scene's one in-flight render. */
+typedef struct rt_ray {
+  double o[3], d[3];
+  double tmax; /* occlusion only */
+} rt_ray;
+typedef struct rt_hit {
+  double t, pos[3], normal[3];
+  int32_t prim, top, material, args;
+  uint32_t flags; /* RT_HIT_* */
+  int32_t pad;
+} rt_hit;
+#define RT_HIT_HIT 1u      /* else a miss: t = +Inf, prim = top = material = -1, pos / normal 0 */
+#define RT_HIT_INSTANCE 2u /* reached through a myInstance */
+#define RT_HIT_IN_ACCEL 4u /* a member of a list / BVH (the Q4 double transform applies to pos / normal) */
+#define RT_HIT_BAD_RAY 8u  /* rejected ray: a miss, never traversed */
+typedef struct rt_trace_params {
+  uint64_t seed, first_key;
+  uint32_t flags, pad; /* RT_TRACE_* */
+} rt_trace_params;
+#define RT_TRACE_ANY 1u     /* occlusion (calcShadow) instead of the closest hit */
+#define RT_TRACE_LANES 2u   /* per-lane reference-order traversal, all fp64 */
+#define RT_TRACE_NOCULL 4u  /* as RT_RENDER_NOCULL: no bounding-sphere cull, no nearest-first order */
+#define RT_TRACE_GENERIC 8u /* the all-features instantiation, as RT_RENDER_GENERIC */
+int rt_trace_rays(rt_scene* scene, const rt_trace_params* p, const rt_ray* rays, int64_t n, rt_hit* hits,
+                  uint8_t* occluded);
+int rt_trace_rays_device(rt_scene* scene, const rt_trace_params* p, const rt_ray* d_rays, int64_t n, rt_hit* d_hits,
+                         uint8_t* d_occluded, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

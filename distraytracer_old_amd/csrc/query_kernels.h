@@ -14,11 +14,10 @@ namespace dv {
 // traversals count the active lanes only (every one is a __ballot under the caller's exec mask, and
 // the wave-uniform frames in LDS are written and read by those same lanes), as in the render kernel,
 // whose invalid pixels and untraced samples stay out of trace_sample.
+// query_ray is the body both kernels below share: ray i of rays, keyed firstKey + i, into hits[i] / occ[i].
 template <uint32_t F, bool PK, bool ANY>
-__global__ void __launch_bounds__(64) query_kernel(SceneD S, uint64_t seed, uint64_t firstKey, const rt_ray* __restrict__ rays,
-                                                   int64_t n, rt_hit* __restrict__ hits, uint8_t* __restrict__ occ) {
-  const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
-  if (i >= n) return;
+__device__ __forceinline__ void query_ray(const SceneD& S, uint64_t seed, uint64_t firstKey, const rt_ray* __restrict__ rays,
+                                          int64_t i, rt_hit* __restrict__ hits, uint8_t* __restrict__ occ) {
   const double* r = (const double*)(rays + i);
   const V o = mk(r[0], r[1], r[2]), d = mk(r[3], r[4], r[5]);
   const double tmax = r[6];
@@ -62,6 +61,25 @@ __global__ void __launch_bounds__(64) query_kernel(SceneD S, uint64_t seed, uint
     }
     hits[i] = h;
   }
+}
+
+template <uint32_t F, bool PK, bool ANY>
+__global__ void __launch_bounds__(64) query_kernel(SceneD S, uint64_t seed, uint64_t firstKey, const rt_ray* __restrict__ rays,
+                                                   int64_t n, rt_hit* __restrict__ hits, uint8_t* __restrict__ occ) {
+  const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  query_ray<F, PK, ANY>(S, seed, firstKey, rays, i, hits, occ);
+}
+
+// RT_TRACE_SORT (ray_sort.hip): lane `slot` handles ray order[slot] of the window -- its key, its record.
+// order is a permutation of [0, n) (sorted iota values), so every index is in range whatever the keys were.
+template <uint32_t F, bool PK, bool ANY>
+__global__ void __launch_bounds__(64) query_kernel_idx(SceneD S, uint64_t seed, uint64_t firstKey,
+                                                       const rt_ray* __restrict__ rays, int64_t n, rt_hit* __restrict__ hits,
+                                                       uint8_t* __restrict__ occ, const uint32_t* __restrict__ order) {
+  const int64_t slot = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (slot >= n) return;
+  query_ray<F, PK, ANY>(S, seed, firstKey, rays, (int64_t)order[slot], hits, occ);
 }
 
 }  // namespace dv

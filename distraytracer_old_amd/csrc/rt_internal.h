@@ -98,6 +98,15 @@ SceneD render_scene_view(const rt_scene* s, uint32_t render_flags);
 // query.hip: the chunk size of rt_trace_rays (scene creation), its buffers freed (rt_scene_destroy)
 void trace_init(rt_scene* s);
 void trace_free(rt_scene* s);
+// ray_sort.hip (RT_TRACE_SORT): the coherence order of device rays [0, n), n <= the scene's sort window, on
+// `stream` (hipStream_t) into the scene's sort scratch (grown first when too small, which synchronises the
+// device): *order = caller indices base + i by ascending sort key, a permutation of [base, base + n).
+// sorted_query traces device rays [0, n) window by window through that order, records at the rays' own
+// indices; sort_free frees the scratch.
+int sort_order(rt_scene* s, const rt_ray* d_rays, int64_t n, uint32_t base, const uint32_t** order, void* stream);
+int sorted_query(rt_scene* s, uint32_t flags, uint64_t seed, uint64_t firstKey, const rt_ray* d_rays, int64_t n, rt_hit* d_hits,
+                 uint8_t* d_occ, void* stream);
+void sort_free(rt_scene* s);
 // group.hip: the deterministic rank plan (rt_rank_plan)
 void plan_ranks(const uint32_t* cost, int n, int world, double heavy, int slots, int32_t* owner, int32_t* order,
                 const double* weight = nullptr);
@@ -155,4 +164,14 @@ struct rt_scene {
   void* traceStage = nullptr;
   size_t traceCap = 0;  // rays
   int64_t traceChunk = 0;
+  // RT_TRACE_SORT (ray_sort.hip): keys and indices (double-buffered), the bounds cell and the sort's
+  // temporary storage of one window in one device allocation (grow-only); the window in rays
+  // (DISTRAYTRACER_SORT_WINDOW) and the key's bits per axis of the origin cell and of the direction
+  // (DISTRAYTRACER_SORT_ORG_BITS, DISTRAYTRACER_SORT_DIR_BITS), read at creation
+  void* sortDev = nullptr;
+  size_t sortCap = 0;     // rays
+  size_t sortTmpCap = 0;  // bytes
+  int64_t sortWindow = 0;
+  int sortOrgBits = 0;
+  int sortDirBits = 0;
 };

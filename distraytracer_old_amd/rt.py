@@ -60,7 +60,9 @@ EXPORTS = ["rt_abi_version", "rt_build_id", "rt_last_error", "rt_device_count", 
            "rt_group_create_comm",
            "rt_photons_build_comm", "rt_photons_build_local",
            # added to ABI 7: ray queries (closest hit / occlusion of caller rays)
-           "rt_trace_rays", "rt_trace_rays_device"]
+           "rt_trace_rays", "rt_trace_rays_device",
+           # added to ABI 7: the coherence order of RT_TRACE_SORT
+           "rt_trace_order", "rt_trace_order_device"]
 
 _lib = None
 
@@ -171,6 +173,10 @@ def lib():
             vp, i64 = ctypes.c_void_p, ctypes.c_int64
             L.rt_trace_rays.argtypes = [vp, vp, vp, i64, vp, vp]
             L.rt_trace_rays_device.argtypes = [vp, vp, vp, i64, vp, vp, vp]
+        if hasattr(L, "rt_trace_order"):  # added to ABI 7
+            vp, i64 = ctypes.c_void_p, ctypes.c_int64
+            L.rt_trace_order.argtypes = [vp, vp, vp, i64, vp]
+            L.rt_trace_order_device.argtypes = [vp, vp, vp, i64, vp, vp]
         _lib = L
     return _lib
 
@@ -539,6 +545,7 @@ TRACE_ANY = 1  # RT_TRACE_ANY: occlusion (calcShadow) instead of the closest hit
 TRACE_LANES = 2  # RT_TRACE_LANES: per-lane reference-order traversal, all fp64
 TRACE_NOCULL = 4  # RT_TRACE_NOCULL: no bounding-sphere cull, no nearest-first order
 TRACE_GENERIC = 8  # RT_TRACE_GENERIC: the all-features instantiation
+TRACE_SORT = 16  # RT_TRACE_SORT: rays reordered for coherence on the device, records at their own indices
 HIT_HIT, HIT_INSTANCE, HIT_IN_ACCEL, HIT_BAD_RAY = 1, 2, 4, 8  # RT_HIT_*
 
 
@@ -756,6 +763,27 @@ class Scene:
         _check(lib().rt_trace_rays_device(self._h, ctypes.byref(p), ctypes.c_void_p(rays_ptr or None), n,
                                           ctypes.c_void_p(hits_ptr or None), ctypes.c_void_p(occ_ptr or None),
                                           ctypes.c_void_p(stream or None)), "rt_trace_rays_device")
+
+    def trace_order(self, o, d, tmax=np.inf, flags=0) -> np.ndarray:
+        """The order a TRACE_SORT trace of the rays runs them in -> uint32 [n]: order[k] is the index of the
+        ray in slot k, a permutation of each sort window's index range (rt_trace_order)."""
+        from .desc import TraceParams
+
+        r = rays(o, d, tmax)
+        order = np.zeros(len(r), dtype=np.uint32)
+        p = TraceParams(0, 0, flags, 0)
+        _check(lib().rt_trace_order(self._h, ctypes.byref(p), r.ctypes.data, len(r), order.ctypes.data), "rt_trace_order")
+        return order
+
+    def trace_order_device(self, rays_ptr: int, n: int, order_ptr: int, stream: int = 0, flags=0):
+        """Asynchronous rt_trace_order of n device rt_ray into a device uint32 [n] buffer on a HIP stream
+        (rt_trace_order_device)."""
+        from .desc import TraceParams
+
+        p = TraceParams(0, 0, flags, 0)
+        _check(lib().rt_trace_order_device(self._h, ctypes.byref(p), ctypes.c_void_p(rays_ptr or None), n,
+                                           ctypes.c_void_p(order_ptr or None), ctypes.c_void_p(stream or None)),
+               "rt_trace_order_device")
 
     def render_pixels_device(self, p: RenderParams, pixels: np.ndarray, rgb_ptr: int, argb_ptr: int, stream: int = 0):
         """Asynchronous one-sample-per-wave render of the listed pixels (host int32 list) into whole-frame buffers."""

@@ -519,6 +519,29 @@ int rt_trace_rays(rt_scene* scene, const rt_trace_params* p, const rt_ray* rays,
                   uint8_t* occluded);
 int rt_trace_rays_device(rt_scene* scene, const rt_trace_params* p, const rt_ray* d_rays, int64_t n, rt_hit* d_hits,
                          uint8_t* d_occluded, void* hip_stream);
+/* Coherence sort (added to ABI 7; probe the two entries below with dlsym). With RT_TRACE_SORT either trace
+   entry reorders the rays on the device before tracing them -- by a key of the origin's cell in a 64^3 grid
+   over the window's valid origins, then of the direction (octahedral map, Morton order) -- so that a wave's
+   64 rays walk similar paths, and writes every record at the ray's own index. Results are the same bytes as
+   without the flag (records with their padding, occlusion bytes): ray i keeps the key first_key + i and
+   its place in the output, rejected rays are reported at their own index. It combines with every other
+   RT_TRACE_* flag. It pays for batches in no particular order (picking, visibility, secondary rays) and
+   costs a little on rays already in a coherent order: DESIGN.md section 11 has the measurements.
+   A batch is sorted in independent windows of at most 2^24 rays (DISTRAYTRACER_SORT_WINDOW, read at scene
+   creation: at least 64, rounded down to a multiple of 64; a testing knob); rt_trace_rays sorts each of
+   its staging chunks on its own. Keys, indices and the sort's temporary storage live in grow-only device
+   buffers the scene owns (rt_scene_destroy frees them; 24 bytes per ray of the largest window sorted, plus the sort's temporary storage).
+   rt_trace_rays_device stays asynchronous on hip_stream, except that a call which needs larger buffers
+   allocates them first, which may synchronise the device. Sorted traces of one scene share those
+   buffers and must not overlap, on any streams: the one-in-flight-render rule.
+   rt_trace_order / rt_trace_order_device: the order alone. order[k] = the caller index of the ray a sorted
+   trace puts in slot k: a permutation of each window's index range, rejected rays in the window's last
+   slots. Host buffers and blocking (windows inside each staging chunk, as rt_trace_rays sorts), or device
+   buffers and asynchronous on hip_stream. n must be < 2^32; n == 0 is RT_OK. For inspection and tests. */
+#define RT_TRACE_SORT 16u
+int rt_trace_order(rt_scene* scene, const rt_trace_params* p, const rt_ray* rays, int64_t n, uint32_t* order);
+int rt_trace_order_device(rt_scene* scene, const rt_trace_params* p, const rt_ray* d_rays, int64_t n, uint32_t* d_order,
+                          void* hip_stream);
 
 #ifdef __cplusplus
 }

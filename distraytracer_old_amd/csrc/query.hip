@@ -160,6 +160,13 @@ void rt::trace_init(rt_scene* s) {
   if (const char* e = std::getenv("DISTRAYTRACER_SORT_DIR_BITS")) s->sortDirBits = std::min(16, std::max(1, std::atoi(e)));
 }
 
+int rt::trace_stage(rt_scene* s, int64_t n, void** stream) {
+  hipStream_t st = nullptr;
+  const int rc = stage_ready(s, n, &st);
+  *stream = st;
+  return rc;
+}
+
 void rt::trace_free(rt_scene* s) {
   stage_free(s);
   sort_free(s);

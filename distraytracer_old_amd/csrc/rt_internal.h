@@ -107,6 +107,13 @@ int sort_order(rt_scene* s, const rt_ray* d_rays, int64_t n, uint32_t base, cons
 int sorted_query(rt_scene* s, uint32_t flags, uint64_t seed, uint64_t firstKey, const rt_ray* d_rays, int64_t n, rt_hit* d_hits,
                  uint8_t* d_occ, void* stream);
 void sort_free(rt_scene* s);
+// shade.hip (rt_shade_rays, rt_camera_rays) borrows two things. query.hip: the scene's stream (hipStream_t
+// in *stream) and rt_trace_rays' staging grown to min(n, traceChunk) rays -- [cap rays][cap hits][cap bytes]
+// on the device (traceDev) and pinned on the host (traceStage), cap = traceCap. trace.hip: the host copies of
+// the Perlin tables (256 and 12 x 3 ints), which every translation unit that reaches the noise textures
+// uploads into its own c_perm / c_grad3.
+int trace_stage(rt_scene* s, int64_t n, void** stream);
+void perlin_tables(const int** perm, const int** grad3);
 // group.hip: the deterministic rank plan (rt_rank_plan)
 void plan_ranks(const uint32_t* cost, int n, int world, double heavy, int slots, int32_t* owner, int32_t* order,
                 const double* weight = nullptr);

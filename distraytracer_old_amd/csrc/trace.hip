@@ -824,6 +824,10 @@ static SceneD launch_scene(const rt_scene* s, uint32_t flags) {
   return sd;
 }
 
+void rt::perlin_tables(const int** perm, const int** grad3) {
+  *perm = H_PERM;
+  *grad3 = &H_GRAD3[0][0];
+}
 uint32_t rt::render_variant_mask(const rt_scene* s, uint32_t render_flags) { return variant_mask(s->hs, render_flags); }
 SceneD rt::render_scene_view(const rt_scene* s, uint32_t render_flags) { return launch_scene(s, render_flags); }
 

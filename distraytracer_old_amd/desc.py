@@ -95,6 +95,12 @@ class TraceParams(ctypes.Structure):
                 ("pad", ctypes.c_uint32)]
 
 
+class ShadeParams(ctypes.Structure):
+    """rt_shade_params: ray i of rt_shade_rays is keyed {seed, pixel = first_key + i, sample}."""
+    _fields_ = [("seed", ctypes.c_uint64), ("first_key", ctypes.c_uint64), ("flags", ctypes.c_uint32),
+                ("sample", ctypes.c_uint32)]
+
+
 # the numpy views of rt_ray / rt_hit arrays (same layout as the ctypes mirrors)
 RAY_DTYPE = np.dtype([("o", "<f8", 3), ("d", "<f8", 3), ("tmax", "<f8")])
 HIT_DTYPE = np.dtype([("t", "<f8"), ("pos", "<f8", 3), ("normal", "<f8", 3), ("prim", "<i4"), ("top", "<i4"),
@@ -103,7 +109,8 @@ assert RAY_DTYPE.itemsize == ctypes.sizeof(Ray) == 56 and HIT_DTYPE.itemsize == 
 
 STRUCTS = {"rt_prim_desc": PrimDesc, "rt_material_desc": MaterialDesc, "rt_light_desc": LightDesc,
            "rt_accel_desc": AccelDesc, "rt_instance_desc": InstanceDesc, "rt_texture_desc": TextureDesc,
-           "rt_scene_desc": SceneDesc, "rt_ray": Ray, "rt_hit": Hit, "rt_trace_params": TraceParams}
+           "rt_scene_desc": SceneDesc, "rt_ray": Ray, "rt_hit": Hit, "rt_trace_params": TraceParams,
+           "rt_shade_params": ShadeParams}
 
 
 class SceneBuilder:

@@ -62,7 +62,9 @@ EXPORTS = ["rt_abi_version", "rt_build_id", "rt_last_error", "rt_device_count", 
            # added to ABI 7: ray queries (closest hit / occlusion of caller rays)
            "rt_trace_rays", "rt_trace_rays_device",
            # added to ABI 7: the coherence order of RT_TRACE_SORT
-           "rt_trace_order", "rt_trace_order_device"]
+           "rt_trace_order", "rt_trace_order_device",
+           # added to ABI 7: radiance queries (the shading tree on caller rays) and a frame's camera rays
+           "rt_shade_rays", "rt_shade_rays_device", "rt_camera_rays", "rt_camera_rays_device"]
 
 _lib = None
 
@@ -177,6 +179,12 @@ def lib():
             vp, i64 = ctypes.c_void_p, ctypes.c_int64
             L.rt_trace_order.argtypes = [vp, vp, vp, i64, vp]
             L.rt_trace_order_device.argtypes = [vp, vp, vp, i64, vp, vp]
+        if hasattr(L, "rt_shade_rays"):  # added to ABI 7
+            vp, i64 = ctypes.c_void_p, ctypes.c_int64
+            L.rt_shade_rays.argtypes = [vp, vp, vp, i64, vp, vp]
+            L.rt_shade_rays_device.argtypes = [vp, vp, vp, i64, vp, vp, vp]
+            L.rt_camera_rays.argtypes = [vp, vp, ctypes.c_int, vp]
+            L.rt_camera_rays_device.argtypes = [vp, vp, ctypes.c_int, vp, vp]
         _lib = L
     return _lib
 
@@ -784,6 +792,47 @@ class Scene:
         _check(lib().rt_trace_order_device(self._h, ctypes.byref(p), ctypes.c_void_p(rays_ptr or None), n,
                                            ctypes.c_void_p(order_ptr or None), ctypes.c_void_p(stream or None)),
                "rt_trace_order_device")
+
+    def shade(self, o, d, seed=0, first_key=0, sample=0, flags=0, status=True):
+        """The colour each ray (o [n, 3], d [n, 3]) sees -> (rgb float64 [n, 3], status uint8 [n]: 0 shaded,
+        2 rejected ray with colour 0; None with status=False). Ray i is shaded under the key the render gives
+        sample `sample` of pixel first_key + i (rt_shade_rays; flags: TRACE_NOCULL / TRACE_GENERIC / TRACE_SORT)."""
+        from .desc import ShadeParams
+
+        r = rays(o, d)
+        rgb = np.zeros((len(r), 3), dtype=np.float64)
+        st = np.zeros(len(r), dtype=np.uint8) if status else None
+        p = ShadeParams(seed, first_key, flags, sample)
+        _check(lib().rt_shade_rays(self._h, ctypes.byref(p), r.ctypes.data, len(r), rgb.ctypes.data,
+                                   st.ctypes.data if status else None), "rt_shade_rays")
+        return rgb, st
+
+    def shade_device(self, rays_ptr: int, n: int, rgb_ptr: int, status_ptr: int = 0, stream: int = 0, seed=0,
+                     first_key=0, sample=0, flags=0):
+        """Asynchronous rt_shade_rays of n device rt_ray (e.g. torch tensors' data_ptr()) into a device
+        float64 [n, 3] buffer and, if given, a uint8 [n] status buffer on a HIP stream (rt_shade_rays_device)."""
+        from .desc import ShadeParams
+
+        p = ShadeParams(seed, first_key, flags, sample)
+        _check(lib().rt_shade_rays_device(self._h, ctypes.byref(p), ctypes.c_void_p(rays_ptr or None), n,
+                                          ctypes.c_void_p(rgb_ptr or None), ctypes.c_void_p(status_ptr or None),
+                                          ctypes.c_void_p(stream or None)), "rt_shade_rays_device")
+
+    def camera_rays(self, W, H, spp=0, seed=0x5EED0001, sample=0) -> np.ndarray:
+        """The rays a W x H render at spp shoots for sample `sample` of every pixel -> desc.RAY_DTYPE [H * W],
+        row-major: index = pixel key (rt_camera_rays). An untraced fisheye sample has d = 0."""
+        from .desc import RAY_DTYPE
+
+        p = params(W, H, spp, seed)
+        r = np.zeros(W * H, dtype=RAY_DTYPE)
+        _check(lib().rt_camera_rays(self._h, ctypes.byref(p), sample, r.ctypes.data), "rt_camera_rays")
+        return r
+
+    def camera_rays_device(self, p: RenderParams, rays_ptr: int, sample: int = 0, stream: int = 0):
+        """Asynchronous rt_camera_rays into a device rt_ray [height * width] buffer on a HIP stream
+        (rt_camera_rays_device)."""
+        _check(lib().rt_camera_rays_device(self._h, ctypes.byref(p), sample, ctypes.c_void_p(rays_ptr or None),
+                                           ctypes.c_void_p(stream or None)), "rt_camera_rays_device")
 
     def render_pixels_device(self, p: RenderParams, pixels: np.ndarray, rgb_ptr: int, argb_ptr: int, stream: int = 0):
         """Asynchronous one-sample-per-wave render of the listed pixels (host int32 list) into whole-frame buffers."""

@@ -543,6 +543,61 @@ int rt_trace_order(rt_scene* scene, const rt_trace_params* p, const rt_ray* rays
 int rt_trace_order_device(rt_scene* scene, const rt_trace_params* p, const rt_ray* d_rays, int64_t n, uint32_t* d_order,
                           void* hip_stream);
 
+/* ---- Radiance queries and camera rays (added to ABI 7; probe the four entries with dlsym) --------------
+   rt_shade_rays / rt_shade_rays_device: what colour each of the caller's rays sees -- the reference's
+   reflectRay (myScene.java:907-914), the whole shading tree the render kernel runs per camera sample:
+   lights and soft shadows, both Fresnel children, textures, the photon gather.
+
+   Ray i is built and rejected exactly as rt_trace_rays builds and rejects it (d normalised once by the
+   myRay constructor; a non-finite component of o or d, a zero d or a NaN tmax rejects the ray). tmax is
+   otherwise ignored. The key contract: ray i is shaded under the RNG key
+       {seed, pixel = first_key + i, sample = p->sample, node 1, camera-ray time site},
+   the key the render gives sample `sample` of pixel first_key + i (pixel = row * width + col). Every draw
+   below the camera ray -- area-light shadow points, a moving object's ray time, the children's keys -- hangs
+   on it, so a ray's colour depends on its key and never on its place in the batch or on its neighbours.
+   rgb[3i .. 3i+2] is the double the shading returns: not converted to float, not averaged, each channel
+   <= 1 (the myColor constructor's clamp). status[i] (status may be NULL) is 0 for a shaded ray; a
+   rejected ray gets colour 0, 0, 0 and status 2 and is never traced.
+
+   The fold that turns per-sample colours into the frame: shade the rays rt_camera_rays emits for sample
+   s = 0 .. spp-1 of a frame with first_key 0, sample s and the frame's seed. At spp == 1 in a scene
+   without depth of field the pixel is the colour as returned; otherwise it is the sum, from +0.0 and in
+   sample order, of the samples with status 0, divided by spp, each channel clamped to <= 1. Converted to
+   float that is rt_render's rgb, and 255 << 24 | (int)(r * 255) << 16 | (int)(g * 255) << 8 |
+   (int)(b * 255) of the doubles its argb, bit for bit.
+
+   flags: RT_TRACE_NOCULL, RT_TRACE_GENERIC and RT_TRACE_SORT as for rt_trace_rays (RT_TRACE_SORT shades
+   through the coherence order and writes every result at the ray's own index: the same bytes). The
+   shading tree is compiled for the packet traversal only: RT_TRACE_LANES, RT_TRACE_ANY and unknown bits
+   are RT_E_INVALID. The kernel is picked by rt_trace_rays' rule. A scene that uses a photon map gets it
+   built on demand with p->seed, as by every render entry.
+
+   rt_shade_rays: host buffers, blocking, on the scene's own stream, staged in chunks through
+   rt_trace_rays' staging buffers. rt_shade_rays_device: device buffers, asynchronous on hip_stream (the
+   first call per device uploads the noise tables first). n == 0 is RT_OK. A shade call counts as the
+   scene's one in-flight render. */
+typedef struct rt_shade_params {
+  uint64_t seed, first_key;
+  uint32_t flags;  /* RT_TRACE_NOCULL | RT_TRACE_GENERIC | RT_TRACE_SORT */
+  uint32_t sample; /* the RNG key's sample index of every ray in the batch */
+} rt_shade_params;
+int rt_shade_rays(rt_scene* scene, const rt_shade_params* p, const rt_ray* rays, int64_t n, double* rgb,
+                  uint8_t* status);
+int rt_shade_rays_device(rt_scene* scene, const rt_shade_params* p, const rt_ray* d_rays, int64_t n, double* d_rgb,
+                         uint8_t* d_status, void* hip_stream);
+/* The rays a render of p shoots for sample `sample` of every pixel, as data: rays[width * height],
+   row-major, so that a ray's index is its pixel's key. p's rows must be the whole image (as for
+   rt_render_pixels_device), spp <= 0 means the scene's own, 0 <= sample < spp; p->flags is ignored. All
+   five camera paths of the render kernel -- field of view at 1 spp (no jitter) and with its y-then-x jitter,
+   depth of field (lens point and focal point), fisheye, orthographic -- with the render's own constants and
+   arithmetic, so o and d are the render's doubles. d is not normalised (the ray constructor does that),
+   tmax is +Inf. A fisheye sample outside the image circle, which the render does not trace, is emitted
+   with d = 0: every query rejects it. With rt_trace_rays the rays also give depth, normal and primitive-id
+   buffers of exactly the frame's rays. rt_camera_rays: a host buffer, blocking; rt_camera_rays_device: a
+   device buffer, asynchronous on hip_stream. */
+int rt_camera_rays(rt_scene* scene, const rt_render_params* p, int sample, rt_ray* rays);
+int rt_camera_rays_device(rt_scene* scene, const rt_render_params* p, int sample, rt_ray* d_rays, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -495,6 +495,12 @@ static int make_params(rt_scene* s, const rt_render_params* p, ParamsD& P) {
   P.G = G;
   P.tw = TW[lg];
   P.th = (64 / G) / P.tw;
+  // the kernels divide by G, tw and th with shifts and masks (dv::pix_geo): powers of two, one wave
+  {
+    const auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
+    if (!pow2(P.G) || !pow2(P.tw) || !pow2(P.th) || P.G * P.tw * P.th != 64)
+      return set_error(RT_E_INVALID, "wave layout: G, tw, th must be powers of two with G * tw * th = 64");
+  }
   P.order = nullptr;
   P.tcost = nullptr;
   // myFOVScene.setSceneParams (myScene.java:1367-1381) at the requested resolution

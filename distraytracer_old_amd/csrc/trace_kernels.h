@@ -3740,6 +3740,17 @@ DEVI int tile_of_block(int b, int ntiles) {
 #ifndef RT_RENDER_WAVES
 #define RT_RENDER_WAVES 4
 #endif
+// The cheaper wave prologue and sums of render_kernel (DESIGN.md §4 "Wave prologue, sums and output"):
+// pixel geometry by shifts, the per-pixel sum on three channel lanes, the average of 2^k samples as a
+// product. On in the variants without transparency, extra cameras, lens or column step (F = 0 and
+// FT_PRIM; C3's gain is in DESIGN.md §6). C4's and C5's variants ran 0.7-1.4 % slower with it through
+// their register allocation, so they, and every other variant, compile the code they had
+// (RT_WAVE_FAST=0: every variant does).
+#ifndef RT_WAVE_FAST
+#define RT_WAVE_FAST 1
+#endif
+template <uint32_t F>
+constexpr bool wave_fast() { return RT_WAVE_FAST != 0 && (F & (FT_TRANS | FT_CAMX | FT_DOF | FT_PASS)) == 0; }
 // where a lane's pixel is: sample lane j of pixel pl of the wave's tile
 struct PixGeo {
   int j, pl, ci, col, ri, row;
@@ -3758,6 +3769,48 @@ DEVI PixGeo pix_geo(int lane, int tile, int tilesX, int ncols, const ParamsD& P)
   const int band = uni_here(P.band);  // (the division's reciprocal is not kept across the sample loop)
   g.row = band == 1 ? P.row0 + g.ri * P.rowStep : P.row0 + (g.ri / band) * P.rowStep * band + g.ri % band;
   return g;
+}
+// pix_geo's values for the wave_fast variants' sample loop. G, tw and th are powers of two
+// (make_params), so the lane's divisions are shifts and masks by their bit positions (one scalar
+// instruction each from the kernel arguments), and band == 1 branches round the band division. In
+// render_kernel's epilogue the same code made the register allocator spill SceneD's pointers
+// (C3 +6 %), so there, and in the other kernels, pix_geo stays.
+template <uint32_t F>
+DEVI PixGeo pix_geo_shift(int lane, int tile, int tilesX, int ncols, const ParamsD& P) {
+  static_assert((F & FT_PASS) == 0, "no column step in the wave_fast variants");
+  PixGeo g;
+  const int band = uni_here(P.band);
+  const int tx = tile % tilesX, ty = tile / tilesX;
+  const int lgG = __builtin_ctz((unsigned)P.G), lgTw = __builtin_ctz((unsigned)P.tw), lgTh = __builtin_ctz((unsigned)P.th);
+  g.j = lane & (P.G - 1);
+  g.pl = lane >> lgG;
+  g.ci = (tx << lgTw) + (g.pl & (P.tw - 1));
+  g.ri = (ty << lgTh) + (g.pl >> lgTw);
+  g.row = P.row0 + g.ri * P.rowStep;
+  if (__builtin_expect(band != 1, 0))  // a branch on the wave-uniform band
+    g.row = P.row0 + (g.ri / band) * P.rowStep * band + g.ri % band;
+  g.col = g.ci;
+  g.valid = g.ci < ncols && g.ri < P.nrows;
+  return g;
+}
+// the sample loop's geometry: by shifts in the wave_fast variants
+template <uint32_t F>
+DEVI PixGeo pix_geo_loop(int lane, int tile, int tilesX, int ncols, const ParamsD& P) {
+  if constexpr (wave_fast<F>()) return pix_geo_shift<F>(lane, tile, tilesX, ncols, P);
+  else return pix_geo<F>(lane, tile, tilesX, ncols, P);
+}
+// the mean of a pixel's n samples from their sums
+template <bool FAST>
+DEVI V sample_mean(double rs, double gs, double bs, int n) {
+  if constexpr (FAST) {
+    if ((n & (n - 1)) == 0) {
+      // n = 2^k: x / n and x * 2^-k round the same real number once, so they are the same double for
+      // every x (subnormal results and non-finite x included); 2^-k is built from its exponent field
+      const double inv = __longlong_as_double((long long)(1023 - __builtin_ctz((unsigned)n)) << 52);
+      return mk(rs * inv, gs * inv, bs * inv);
+    }
+  }
+  return mk(rs / n, gs / n, bs / n);
 }
 // the lane index as an opaque value: what is derived from it is recomputed where it is used
 // instead of being hoisted out of the sample loop and kept (spilled) across the shading tree
@@ -3795,7 +3848,8 @@ render_kernel(SceneD S, ParamsD P, float* __restrict__ rgb, int32_t* __restrict_
   // columns 0, colStep, ... of a refine pass; the other kernels render every column (the
   // column-step arithmetic alone cost the C3 kernel 2.4 %)
   const int ncols = (F & FT_PASS) ? (P.W + P.colStep - 1) / P.colStep : P.W;
-  const int tilesX = (ncols + P.tw - 1) / P.tw;
+  constexpr bool FAST = wave_fast<F>();
+  const int tilesX = FAST ? (ncols + P.tw - 1) >> __builtin_ctz((unsigned)P.tw) : (ncols + P.tw - 1) / P.tw;  // tw: a power of two
   int tile = tile_of_block(blockIdx.x, tilesX * ((P.nrows + P.th - 1) / P.th));
   if (tile < 0) return;  // padding block of the XCD mapping (whole workgroup)
   if (P.order) tile = P.order[tile];
@@ -3836,11 +3890,11 @@ render_kernel(SceneD S, ParamsD P, float* __restrict__ rgb, int32_t* __restrict_
   double rs = 0, gs = 0, bs = 0;
   lds_f64* sums = (lds_f64*)((lds_u8*)rt_lds + LDS_BYTES);
   if (SUMS_LDS && G > 1 && (lane & (G - 1)) == 0) {
-    const int p = lane / G;
+    const int p = FAST ? lane >> __builtin_ctz((unsigned)G) : lane / G;
     sums[3 * p] = 0; sums[3 * p + 1] = 0; sums[3 * p + 2] = 0;
   }
   for (int s0 = 0; s0 < n; s0 += G) {
-    const PixGeo g = pix_geo<F>(opaque_lane(lane), tile, tilesX, ncols, P);
+    const PixGeo g = pix_geo_loop<F>(opaque_lane(lane), tile, tilesX, ncols, P);
     const int j = g.j, pl = g.pl, col = g.col, row = g.row;
     const bool valid = g.valid;
     const double rayY = (-1 * (row - uni_here(P.H) / 2.0));
@@ -3929,6 +3983,41 @@ render_kernel(SceneD S, ParamsD P, float* __restrict__ rgb, int32_t* __restrict_
         if (n == 1 && !dof) { rs = cc.x; gs = cc.y; bs = cc.z; }
         else if (traced) { rs += cc.x; gs += cc.y; bs += cc.z; }
       }
+    } else if constexpr (FAST) {
+      // Every sample lane of a round (valid pixel, s < n) was traced: these variants have no camera
+      // that leaves a sample out, so no flag is stored or tested. The sample lane and the pixel slot
+      // are taken again from the opaque lane index (a mask and a shift), so that nothing of the
+      // round's geometry has to stay in registers across the shading tree.
+      static_assert(SUMS_LDS, "the wave_fast variants keep their sums in LDS");
+      const int ln = opaque_lane(lane);
+      const int jq = ln & (G - 1), pq = ln >> __builtin_ctz((unsigned)G);
+      cbuf[4 * ln + 0] = cc.x;
+      cbuf[4 * ln + 1] = cc.y;
+      cbuf[4 * ln + 2] = cc.z;
+      __syncthreads();
+      const int m = (n - s0) < G ? (n - s0) : G;
+      if (G >= 4) {  // lane c < 3 of a pixel adds channel c: one LDS read and one add per sample
+        if (jq < 3) {
+          double a = sums[3 * pq + jq];
+          const double* b = cbuf + 4 * (ln - jq) + jq;  // channel jq of the pixel's sample 0
+          int q = 0;
+#pragma unroll 1
+          for (; q + 4 <= m; q += 4) {  // four reads in flight; the adds stay in sample order
+            const double v0 = b[4 * q], v1 = b[4 * q + 4], v2 = b[4 * q + 8], v3 = b[4 * q + 12];
+            a += v0; a += v1; a += v2; a += v3;
+          }
+          for (; q < m; ++q) a += b[4 * q];
+          sums[3 * pq + jq] = a;
+        }
+      } else if (jq == 0) {  // G == 2: the pixel's first lane adds the three channels
+        double sr = sums[3 * pq], sg = sums[3 * pq + 1], sb = sums[3 * pq + 2];
+        for (int q = 0; q < m; ++q) {
+          const double* b = cbuf + 4 * (ln + q);
+          sr += b[0]; sg += b[1]; sb += b[2];
+        }
+        sums[3 * pq] = sr; sums[3 * pq + 1] = sg; sums[3 * pq + 2] = sb;
+      }
+      __syncthreads();
     } else {
       cbuf[4 * lane + 0] = cc.x;
       cbuf[4 * lane + 1] = cc.y;
@@ -3957,7 +4046,7 @@ render_kernel(SceneD S, ParamsD P, float* __restrict__ rgb, int32_t* __restrict_
     else if (b[3] != 0) { rs = 0 + b[0]; gs = 0 + b[1]; bs = 0 + b[2]; }  // the sum of one sample
   }
   if (g.valid && g.j == 0) {
-    V c = (n == 1 && !dof) ? mk(rs, gs, bs) : clampc(mk(rs / n, gs / n, bs / n));
+    V c = (n == 1 && !dof) ? mk(rs, gs, bs) : clampc(sample_mean<FAST>(rs, gs, bs, n));
     const size_t o = (size_t)g.ri * ncols + g.ci;
     if (rgb) {
       rgb[3 * o + 0] = (float)c.x;

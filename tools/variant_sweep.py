@@ -162,6 +162,8 @@ VARIANTS = {  # name -> -D defines; names like "s12w4" are parsed (see defines_o
     "tph01": ["RT_F32_TRI_PH_ANY=0", "RT_F32_TRI_PH_CPK=1"],  # photon variant: the triangle pre-test in its closest hit
     "tph11": ["RT_F32_TRI_PH_ANY=1", "RT_F32_TRI_PH_CPK=1"],  # ... in both traversals
     "nosample": ["RT_PROF_NOSAMPLE"],         # camera setup, sums and output alone (results differ)
+    "wf0": ["RT_WAVE_FAST=0"],                # wave prologue / sums as before: divisions, one summing lane, / n
+    "wf0ns": ["RT_WAVE_FAST=0", "RT_PROF_NOSAMPLE"],
     "pers": ["RT_PERSIST=1"],                 # persistent render launches: resident grid, tiles from a ticket counter
     "c4mr": ["@trace.hip:-Xarch_device", "@trace.hip:-mllvm=--amdgpu-sched-strategy=iterative-minreg",
              "@trace.hip:-Xarch_device", "@trace.hip:-mllvm=--amdgpu-use-amdgpu-trackers=1"],

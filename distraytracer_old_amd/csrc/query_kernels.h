@@ -57,7 +57,11 @@ __device__ __forceinline__ void query_ray(const SceneD& S, uint64_t seed, uint64
       h.top = b.top;
       h.material = hr.mat;
       h.args = hr.args;
-      h.flags = RT_HIT_HIT | (((F & FT_INST) && b.inst >= 0) ? RT_HIT_INSTANCE : 0u) | (b.inAcc ? RT_HIT_IN_ACCEL : 0u);
+      // Best.inAcc says which CTM make_hit takes, and is 0 for an instanced primitive; one held by a list
+      // (a sierpinski element) is still a list member whose hit reCalcCTMHitNorm rebuilds (PrimD.xfc >= 0)
+      bool inAcc = b.inAcc != 0;
+      if constexpr ((F & FT_INST) != 0) inAcc = inAcc || (b.inst >= 0 && S.prim[b.inst].xfc >= 0);
+      h.flags = RT_HIT_HIT | (((F & FT_INST) && b.inst >= 0) ? RT_HIT_INSTANCE : 0u) | (inAcc ? RT_HIT_IN_ACCEL : 0u);
     }
     hits[i] = h;
   }

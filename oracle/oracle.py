@@ -62,6 +62,9 @@ def lib():
         L.oracle_camera_hits.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
         L.oracle_knn.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p,
                                  ctypes.c_void_p, ctypes.c_int]
+        u64, dp = ctypes.c_uint64, ctypes.c_void_p
+        L.oracle_trace_rays.argtypes = [dp, dp, ctypes.c_int64, u64, u64, dp, dp, dp, dp, dp, dp, dp, ctypes.c_int]
+        L.oracle_shade_rays.argtypes = [dp, dp, ctypes.c_int64, u64, u64, ctypes.c_uint32, dp, dp, ctypes.c_int]
         _lib = L
     return _lib
 
@@ -138,6 +141,49 @@ class OracleScene:
         if lib().oracle_camera_hits(self._h, W, H, m.ctypes.data, nt) != 0:
             raise RuntimeError("oracle_camera_hits: " + lib().oracle_last_error().decode())
         return m
+
+    @staticmethod
+    def _rays(o, d, tmax=np.inf) -> np.ndarray:
+        o = np.asarray(o, dtype=np.float64).reshape(-1, 3)
+        r = np.empty((len(o), 7), dtype=np.float64)
+        r[:, 0:3] = o
+        r[:, 3:6] = np.asarray(d, dtype=np.float64).reshape(-1, 3)
+        r[:, 6] = tmax
+        return r
+
+    def trace(self, o, d, seed: int = 0, first_key: int = 0, tmax=np.inf, threads: int = 0) -> dict:
+        """findClosestRayHit of the caller's rays, field by field as rt_trace_rays reports it: a dict of
+        hit / instance / in_accel / bad (bool), prim / top / args (int32), t, pos, normal (float64), fp
+        [n, 13] (the hit shader's value fingerprint) and gap (relative difference of the two smallest
+        candidate t). tmax only feeds the rejection rule (a NaN rejects the ray)."""
+        r = self._rays(o, d, tmax)
+        n = len(r)
+        t = np.zeros(n); pos = np.zeros((n, 3)); nrm = np.zeros((n, 3)); fp = np.zeros((n, 13)); gap = np.zeros(n)
+        ints = np.zeros((n, 4), dtype=np.int32)
+        nt = threads if threads > 0 else min(16, os.cpu_count() or 1)
+        lib().oracle_trace_rays(self._h, r.ctypes.data, n, seed, first_key, t.ctypes.data, pos.ctypes.data, nrm.ctypes.data,
+                                ints.ctypes.data, fp.ctypes.data, gap.ctypes.data, None, nt)
+        fl = ints[:, 3]
+        return {"hit": (fl & 1) != 0, "instance": (fl & 2) != 0, "in_accel": (fl & 4) != 0, "bad": (fl & 8) != 0,
+                "prim": ints[:, 0].copy(), "top": ints[:, 1].copy(), "args": ints[:, 2].copy(), "t": t, "pos": pos,
+                "normal": nrm, "fp": fp, "gap": gap}
+
+    def occluded(self, o, d, tmax, seed: int = 0, first_key: int = 0, threads: int = 0) -> np.ndarray:
+        """calcShadow with dist = tmax: uint8 [n], 1 occluded, 0 free, 2 rejected."""
+        r = self._rays(o, d, tmax)
+        occ = np.zeros(len(r), dtype=np.uint8)
+        nt = threads if threads > 0 else min(16, os.cpu_count() or 1)
+        lib().oracle_trace_rays(self._h, r.ctypes.data, len(r), seed, first_key, None, None, None, None, None, None,
+                                occ.ctypes.data, nt)
+        return occ
+
+    def shade(self, o, d, seed: int = 0, first_key: int = 0, sample: int = 0, threads: int = 0):
+        """reflectRay of the caller's rays as rt_shade_rays documents it: (rgb float64 [n, 3], status uint8 [n])."""
+        r = self._rays(o, d)
+        rgb = np.zeros((len(r), 3)); status = np.zeros(len(r), dtype=np.uint8)
+        nt = threads if threads > 0 else min(16, os.cpu_count() or 1)
+        lib().oracle_shade_rays(self._h, r.ctypes.data, len(r), seed, first_key, sample, rgb.ctypes.data, status.ctypes.data, nt)
+        return rgb, status
 
     def close(self):
         if self._h:

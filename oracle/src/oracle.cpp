@@ -109,7 +109,17 @@ struct Hit {  // rayHit (myRay.java:130-186)
   int args[2] = {0, 0};
   double ltMult = 1;
   double phtnPwr[3] = {0, 0, 0};
+  bool viaInst = false;  // reached through a myInstance (oracle_trace_rays)
+  bool inAccel = false;  // left a list's traverse: reCalcCTMHitNorm applied (oracle_trace_rays)
 };
+
+// oracle_trace_rays only: the two smallest candidate t of one query, over every primitive-level hit
+// the reference's loops see (objList entries and list members; accels report their members).
+struct TTrack {
+  double t1 = DMAX, t2 = DMAX;
+  void add(double t) { if (t < t1) { t2 = t1; t1 = t; } else if (t < t2) t2 = t; }
+};
+static thread_local TTrack* g_track = nullptr;
 
 // stats shared with the product's counters (layout in DESIGN.md "Counters")
 enum { ST_CAM = 0, ST_SHADOW, ST_REFL, ST_REFR, ST_BOX, ST_TRI, ST_QUAD, ST_SPHERE, ST_LIGHT, ST_PHOTON, ST_TEXEL, ST_N = 16 };
@@ -135,6 +145,7 @@ struct GeomBase {
   virtual V3 normalAt(const V3& pt, const int* args) = 0;
   virtual void txtrCoords(const V3& pt, const int* args, const Texture& tex, double time, double& u, double& v) { u = v = 0; }
   virtual bool isAccel() const { return false; }
+  virtual bool holdsAccel() const { return isAccel(); }  // an accel, or an instance of one
 };
 
 // objHit (myRay.java:119-125) + rayHit ctor (myRay.java:147-161)
@@ -586,6 +597,7 @@ struct GeomList : AccelStruct {  // :251-306
     for (GeomBase* o : objs) {
       Ray otr = transformed(ray, o->ctm->inv, o->key);
       Hit h = o->intersect(ray, otr, o->ctm.get(), st);
+      if (g_track && h.isHit && !o->holdsAccel()) g_track->add(h.t);
       if (h.t < clsT) {
         clsObj = o; cls = h; clsT = h.t; clsTr = otr; have = true;
       }
@@ -603,6 +615,7 @@ struct GeomList : AccelStruct {  // :251-306
     n = xvec(nc->adj, n);
     normalize_ip(n);
     cls.objNorm = n;
+    cls.inAccel = true;
     return cls;
   }
 };
@@ -639,12 +652,14 @@ struct Instance : GeomBase {
   Hit intersect(Ray&, Ray& tr, const CTM* ctara, uint64_t* st) override {
     Hit h = obj->intersect(tr, tr, ctara, st);
     if (useShader) h.shdr = shdr;
+    h.viaInst = h.isHit;
     return h;
   }
   int shadowHit(Ray&, Ray& tr, const CTM* ctara, double d, uint64_t* st) override {
     return obj->shadowHit(tr, tr, ctara, d, st);
   }
   V3 normalAt(const V3& p, const int* a) override { return obj->normalAt(p, a); }
+  bool holdsAccel() const override { return obj->holdsAccel(); }
   V3 getOrigin(double t) override { return xpt(obj->ctm->g, obj->getOrigin(t)); }
   V3 getMaxVec() override { return xpt(obj->ctm->g, obj->getMaxVec()); }
   V3 getMinVec() override { return xpt(obj->ctm->g, obj->getMinVec()); }
@@ -2474,6 +2489,98 @@ int oracle_camera_hits(void* p, int W, int H, uint8_t* mask, int nthreads) {
       r.key.pixel = (uint64_t)row * (uint64_t)W + (uint64_t)col; r.key.sample = 0; r.key.node = 1;
       mask[(size_t)row * W + col] = closest_hit(s, r, st).isHit ? 1 : 0;
     }
+  }
+  return 0;
+}
+
+// ---- the caller's own rays (mirrors rt_trace_rays / rt_shade_rays, include/distraytracer.h) --------
+// rays[7*i..]: o, d, tmax. The header's rejection rule: a non-finite component of o or d, a zero d or a
+// NaN tmax. Ray i is Ray(o, d, 0) (the myRay constructor normalises d once), keyed
+// {seed, first_key + i, sample, node 1, site}.
+static bool caller_ray(const double* r, uint64_t seed, uint64_t pixel, uint32_t sample, uint32_t site, Ray& out) {
+  for (int c = 0; c < 6; ++c) if (!std::isfinite(r[c])) return false;
+  if ((r[3] == 0 && r[4] == 0 && r[5] == 0) || r[6] != r[6]) return false;
+  out = Ray(V3(r[0], r[1], r[2]), V3(r[3], r[4], r[5]), 0);
+  out.key.seed = seed; out.key.pixel = pixel; out.key.sample = sample; out.key.node = 1; out.key.time_site = site;
+  return true;
+}
+
+enum { OT_HIT = 1, OT_INSTANCE = 2, OT_IN_ACCEL = 4, OT_BAD_RAY = 8, OT_NFP = 13 };  // RT_HIT_*'s values
+
+// myScene.findClosestRayHit (:888-903) per ray, keeping the winning objList index, or myScene.calcShadow
+// (:879-885) with dist = tmax where occ != NULL (then the record arrays may be NULL).
+// t[n] = rayHit.t, pos / normal[3n] = fwdTransHitLoc / objNorm, ints[4n] = {prim (the primitive's creation
+// index), top, args[0] (box: args[1], the plane index), flags}, fp[13n] = the hit shader's value fingerprint
+// (diffuse, ambient, specular, phongExp, KRefl, KTrans, texture kind), gap[n] = the relative difference of
+// the ray's two smallest candidate t (+Inf: fewer than two). A miss: t = +Inf, prim = top = -1, rest 0.
+// Planar objects keep both orientations precomputed (PlanarState) and normalise a copy of N, so every
+// record is the first-hit value whatever rays came before it.
+int oracle_trace_rays(void* p, const double* rays, int64_t n, uint64_t seed, uint64_t first_key, double* t, double* pos,
+                      double* normal, int32_t* ints, double* fp, double* gap, uint8_t* occ, int nthreads) {
+  Scene* s = (Scene*)p;
+#pragma omp parallel for schedule(dynamic, 64) num_threads(nthreads > 0 ? nthreads : 1)
+  for (int64_t i = 0; i < n; ++i) {
+    Ray ray;
+    const bool ok = caller_ray(rays + 7 * i, seed, first_key + (uint64_t)i, 0, occ ? SITE_SHADOW_TIME : SITE_TIME, ray);
+    if (occ) {
+      occ[i] = ok ? (uint8_t)calc_shadow(s, ray, rays[7 * i + 6], nullptr) : 2;
+      continue;
+    }
+    t[i] = std::numeric_limits<double>::infinity();
+    gap[i] = std::numeric_limits<double>::infinity();
+    for (int c = 0; c < 3; ++c) pos[3 * i + c] = normal[3 * i + c] = 0;
+    for (int c = 0; c < OT_NFP; ++c) fp[OT_NFP * i + c] = 0;
+    int32_t* I = ints + 4 * i;
+    I[0] = I[1] = -1; I[2] = 0; I[3] = ok ? 0 : OT_BAD_RAY;
+    if (!ok) continue;
+    TTrack tr;
+    g_track = &tr;
+    Hit best;
+    int top = -1;
+    for (size_t k = 0; k < s->objList.size(); ++k) {  // closest_hit with the index kept
+      GeomBase* o = s->objList[k];
+      Ray trn = transformed(ray, o->ctm->inv, o->key);
+      Hit h = o->intersect(ray, trn, o->ctm.get(), nullptr);
+      if (h.isHit && !o->holdsAccel()) tr.add(h.t);
+      if (h.isHit && h.t < best.t) { best = h; top = (int)k; }
+    }
+    g_track = nullptr;
+    if (!best.isHit) continue;
+    t[i] = best.t;
+    const V3 &P = best.fwdTransHitLoc, &N = best.objNorm;
+    pos[3 * i] = P.x; pos[3 * i + 1] = P.y; pos[3 * i + 2] = P.z;
+    normal[3 * i] = N.x; normal[3 * i + 1] = N.y; normal[3 * i + 2] = N.z;
+    I[0] = (int32_t)best.obj->key;
+    I[1] = top;
+    I[2] = dynamic_cast<RndrdBox*>(best.obj) ? best.args[1] : best.args[0];
+    I[3] = OT_HIT | (best.viaInst ? OT_INSTANCE : 0) | (best.inAccel ? OT_IN_ACCEL : 0);
+    if (const Shader* sh = best.shdr) {
+      const double v[OT_NFP] = {sh->diffuse.r, sh->diffuse.g, sh->diffuse.b, sh->ambient.r, sh->ambient.g, sh->ambient.b,
+                                sh->specular.r, sh->specular.g, sh->specular.b, sh->phongExp, sh->KRefl, sh->KTrans,
+                                (double)sh->tex};
+      for (int c = 0; c < OT_NFP; ++c) fp[OT_NFP * i + c] = v[c];
+    }
+    if (tr.t2 != DMAX) gap[i] = std::fabs(tr.t2 - tr.t1) / std::max(std::fabs(tr.t2), std::fabs(tr.t1));
+  }
+  return 0;
+}
+
+// myScene.reflectRay (:907-914) of the caller's rays under the key {seed, first_key + i, sample, node 1,
+// SITE_TIME}: rgb[3n] the myColor's doubles, status[n] 0, or 2 with colour 0 for a rejected ray. Like
+// oracle_render it builds the photon map on demand with `seed`.
+int oracle_shade_rays(void* p, const double* rays, int64_t n, uint64_t seed, uint64_t first_key, uint32_t sample, double* rgb,
+                      uint8_t* status, int nthreads) {
+  Scene* s = (Scene*)p;
+  if (s->usePhotonMap && !s->photonsBuilt) send_photons(s, seed);
+#pragma omp parallel for schedule(dynamic, 64) num_threads(nthreads > 0 ? nthreads : 1)
+  for (int64_t i = 0; i < n; ++i) {
+    Ray ray;
+    uint64_t st[ST_N] = {0};
+    Color c(0, 0, 0);
+    const bool ok = caller_ray(rays + 7 * i, seed, first_key + (uint64_t)i, sample, SITE_TIME, ray);
+    if (ok) c = reflect_ray(s, ray, st);
+    rgb[3 * i] = c.r; rgb[3 * i + 1] = c.g; rgb[3 * i + 2] = c.b;
+    if (status) status[i] = ok ? 0 : 2;
   }
   return 0;
 }

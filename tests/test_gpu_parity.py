@@ -207,7 +207,9 @@ def test_knn_u16_bucket_fallback_renders_identically(monkeypatch):
 
 @pytest.mark.parametrize("cli,W,spp", [("c3_bun69k.cli", 128, 2), ("t01.cli", 128, 1), ("p2_t05.cli", 96, 2),
                                        ("c2clear.cli", 96, 1), ("plnts3ColsBunnies.cli", 96, 1),
-                                       ("t11.cli", 64, 1), ("p3_t11_sierp.cli", 64, 1)])
+                                       ("t11.cli", 64, 1), ("p3_t11_sierp.cli", 64, 1),
+                                       # box, plane, hollow cylinder, cylinders
+                                       ("p3_t04.cli", 64, 1), ("old_t08.cli", 64, 1), ("t06.cli", 64, 1), ("old_t05a.cli", 64, 1)])
 def test_specialised_kernel_equals_generic(cli, W, spp):
     """The feature-specialised kernel variant picked for a scene renders bit-identically
     to the all-features kernel (RT_RENDER_GENERIC)."""
@@ -253,7 +255,8 @@ def test_compacted_shadow_rays_render_identically(cli, W, spp):
 
 @pytest.mark.parametrize("cli,W,spp", [("plnts3ColsBunnies.cli", 128, 4), ("p2_t03.cli", 96, 2),
                                        ("c3spotLight.cli", 96, 2), ("p2_t05.cli", 96, 2), ("c4.cli", 96, 2),
-                                       ("cylinder1.cli", 96, 2)])
+                                       ("cylinder1.cli", 96, 2),
+                                       ("p3_t04.cli", 64, 1), ("old_t08.cli", 64, 1), ("t06.cli", 64, 1), ("old_t05a.cli", 64, 1)])
 def test_wave_shadow_cull_renders_identically(cli, W, spp):
     """The wave-level shadow candidate test (SCENE_WAVE_CULL: an entry whose bounding sphere
     stays farther than the lanes' spread from the wave's first shadow segment is skipped) gives
@@ -370,7 +373,8 @@ def test_more_than_64_top_level_entries(tmp_path, n_side):
 @pytest.mark.parametrize("cli,W,spp", [("plnts3ColsBunnies.cli", 96, 4), ("c2clear.cli", 96, 1), ("trTrans.cli", 96, 2),
                                        ("c3_bun69k.cli", 128, 4), ("p2_t07.cli", 96, 2), ("old_t10.cli", 96, 4),
                                        ("t11.cli", 64, 2), ("p3_t11_sierp.cli", 64, 1), ("c4InSphere.cli", 96, 1),
-                                       ("t01.cli", 96, 1)])
+                                       ("t01.cli", 96, 1),
+                                       ("p3_t04.cli", 64, 1), ("old_t08.cli", 64, 1), ("t06.cli", 64, 1), ("old_t05a.cli", 64, 1)])
 def test_wavefront_renders_identically(cli, W, spp):
     """RT_RENDER_WAVEFRONT (level-synchronous shading: one launch per generation of the shading tree,
     children compacted into the next level's queue, frames folded bottom up) renders the monolithic

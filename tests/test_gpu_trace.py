@@ -84,7 +84,8 @@ def _same_bits(a, b, fields=("flags", "prim", "top", "t")):
 
 # ---- 1. camera rays against the oracle's hit mask --------------------------------------------------
 CAMERA = [("c3_bun69k.cli", 64), ("plnts3ColsBunnies.cli", 64), ("p3_t02.cli", 64), ("p2_t03.cli", 64),
-          ("cylinder1.cli", 64), ("desc_bun500.cli", 128)]
+          ("cylinder1.cli", 64), ("desc_bun500.cli", 128),
+          ("p3_t04.cli", 64), ("old_t08.cli", 64), ("t06.cli", 64), ("old_t05a.cli", 64)]  # box, plane, hollow cylinder, cylinders
 
 
 @pytest.mark.parametrize("cli,W", CAMERA, ids=[c for c, _ in CAMERA])

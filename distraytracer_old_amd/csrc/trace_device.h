@@ -48,6 +48,20 @@ DEVI V nrmz(V a) {  // myVector._normalize: division, no-op on zero
   if (m == 0) return a;
   return mk(a.x / m, a.y / m, a.z / m);
 }
+// nrmz that also returns the magnitude it divided by (0 for the zero vector)
+DEVI V nrmz_m(V a, double& m) {
+  m = mag(a);
+  if (m == 0) return a;
+  return mk(a.x / m, a.y / m, a.z / m);
+}
+// nrmz(a) == a, known from the squared length alone: with s = (x^2 + y^2) + z^2 as mag() sums it,
+// s == 1 or s == 1 + 2^-52 gives RN(sqrt(s)) == 1 exactly (sqrt(1 + 2^-52) = 1 + 2^-53 - 2^-107..,
+// below the midpoint of 1 and 1 + 2^-52), and a / 1 == a in every component ("Known
+// normalisations"). Sufficient, not necessary: false only sends the caller to the full nrmz.
+DEVI bool unit_len(V a) {
+  const double s = ((a.x * a.x) + (a.y * a.y)) + (a.z * a.z);
+  return s == 1.0 || s == 1.0 + 0x1p-52;
+}
 DEVI bool veq(V a, V b) { return a.x == b.x && a.y == b.y && a.z == b.z; }
 DEVI V ld3(const double* p) { return mk(p[0], p[1], p[2]); }
 DEVI double jmin(double a, double b) { return (a != a) ? a : ((a <= b) ? a : b); }  // Math.min (finite paths)
@@ -120,8 +134,17 @@ struct WRay {
   bool stable;  // normalize(d) == d
   bool moved;   // d changed since the cached accel-space ray was built
 };
+// UNIT (RT_RENORM_UNIT, default 1, in the variants of known_norm<F>(), trace_kernels.h): a direction of
+// unit_len() is flagged stable without the confirming normalisation -- d, ver and moved stay as they
+// are, which is the state the full path leaves when it finds n == d, in the same call (0: the
+// comparison only).
+#ifndef RT_RENORM_UNIT
+#define RT_RENORM_UNIT 1
+#endif
+template <bool UNIT>
 DEVI void renorm(WRay& r) {
   if (!r.stable) {
+    if (UNIT && unit_len(r.d)) { r.stable = true; return; }
     V n = nrmz(r.d);
     r.stable = veq(n, r.d);
     if (!r.stable) { r.moved = true; r.ver++; }
@@ -351,7 +374,10 @@ struct LimShadow {
   DEVI bool ok(double t) const { return (dist - t) > EPS; }
 };
 
-template <int NV, bool PLANE, class LIM = LimNone>
+#ifndef RT_PLANAR_SIGN
+#define RT_PLANAR_SIGN 1
+#endif
+template <int NV, bool PLANE, bool SIGN = false, class LIM = LimNone>
 DEVI bool planar_test(const double (*v)[3], V nA, V nB, double dA, double dB, V o, V d, double& t, int& st,
                       const LIM& lim = LIM()) {
   double pr = dot(nA, d);
@@ -365,7 +391,12 @@ DEVI bool planar_test(const double (*v)[3], V nA, V nB, double dA, double dB, V 
   } else {
     N = nA; D = dA; st = 0;
   }
-  t = -(dot(N, o) + D) / pr;
+  // SIGN (RT_PLANAR_SIGN, default 1, the triangles of the known_norm<F>() variants): pr < 0 here (not
+  // 0, not NaN), so t = -num / pr is positive only for num > 0; a num that is <= 0, -0 or NaN gives
+  // t <= 0, -0 or NaN, which t > EPS rejects below: the same false without the division
+  const double num = dot(N, o) + D;
+  if (SIGN && !(num > 0)) return false;
+  t = -num / pr;
   if (!(t > EPS)) return false;
   if (PLANE) return true;
   if (!lim.ok(t)) return false;
@@ -382,11 +413,11 @@ DEVI bool planar_test(const double (*v)[3], V nA, V nB, double dA, double dB, V 
   return true;
 }
 
-template <class LIM = LimNone, class TR = TriD>  // TR: TriD or its geometry part (TriG)
+template <bool SIGN, class LIM = LimNone, class TR = TriD>  // TR: TriD or its geometry part (TriG)
 DEVI bool tri_test(const TR& T, V o, V d, double& t, int& st, const LIM& lim = LIM()) {
   V nA = ld3(T.n);
   V nB = mk(-nA.x, -nA.y, -nA.z);  // exactly the reversed-order normal
-  return planar_test<3, false>(T.v, nA, nB, T.dA, T.dB, o, d, t, st, lim);
+  return planar_test<3, false, SIGN>(T.v, nA, nB, T.dA, T.dB, o, d, t, st, lim);
 }
 
 // SL: the primitive record sits at a wave-uniform address (the packet kernels' top-level scans) and

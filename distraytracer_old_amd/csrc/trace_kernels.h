@@ -33,6 +33,26 @@ enum : uint32_t {
   FT_ALL = 1023
 };
 
+// Known normalisations: renorm's unit-length shortcut, make_hit's reuse of the
+// ray's direction, the light distance from the normalisation's magnitude and the triangle test's sign
+// test, each behind its macro (RT_RENORM_UNIT, RT_HIT_DW, RT_LIGHT_DIST, RT_PLANAR_SIGN; default 1),
+// in the triangles-only variants without transparent materials. The others compile the statements as
+// they were: the transparent variants (C4's, C5's kernels) measured 2.9 % / 1.7 % slower with the parts
+// on (profiles/r08a_ab.log), their kernels spilling more, and the F = FT_PRIM kernel's static
+// v_readlane count rose from 872 to 1,129 (such a build is not run).
+#ifndef RT_HIT_DW
+#define RT_HIT_DW 1
+#endif
+#ifndef RT_LIGHT_DIST
+#define RT_LIGHT_DIST 1
+#endif
+template <uint32_t F>
+constexpr bool known_norm() { return (F & (FT_TRANS | FT_PRIM)) == 0; }
+template <uint32_t F> static constexpr bool KN_UNIT = RT_RENORM_UNIT != 0 && known_norm<F>();
+template <uint32_t F> static constexpr bool KN_SIGN = RT_PLANAR_SIGN != 0 && known_norm<F>();
+template <uint32_t F> static constexpr bool KN_DW = RT_HIT_DW != 0 && known_norm<F>();
+template <uint32_t F> static constexpr bool KN_DIST = RT_LIGHT_DIST != 0 && known_norm<F>();
+
 static __constant__ int c_perm[256];  // one copy per translation unit (trace.hip uploads its own)
 static __constant__ int c_grad3[12][3];
 
@@ -85,7 +105,7 @@ DEVI bool test_ref(const SceneD& S, int32_t ref, V o, V d, const Key& k, double&
   if (!(F & FT_PRIM) || ref >= 0) {
     if (CNT) ct.c[C_TRI]++;
     if (WAVE) WCNT(C_WTRI, 1); else if (CNT) ct.c[C_WTRI]++;
-    return tri_test(S.tri[ref], o, d, t, args, lim);
+    return tri_test<KN_SIGN<F>>(S.tri[ref], o, d, t, args, lim);
   }
   const PrimD& P = S.prim[~ref];
   if (CNT) {
@@ -310,7 +330,7 @@ DEVI bool test_ref_u(const SceneD& S, int32_t ref, V o, V d, const Key& k, doubl
       if (CNT) ct.c[C_TRI]++;
       WCNT(C_WTRI, 1);
       const TriG T = sload_tri(S.tri + ref);
-      return tri_test(T, o, d, t, args, lim);
+      return tri_test<KN_SIGN<F>>(T, o, d, t, args, lim);
     }
   }
   return test_ref<CNT, F, LIM, PK>(S, ref, o, d, k, t, args, ct, lim);
@@ -368,7 +388,7 @@ DEVI void leaf_closest(const SceneD& S, int32_t leaf, int accXf, V ao, V ad, WRa
   for (int i = 0; i < lf.count; ++i) {
     if (PK) PKSTAT(P_CT_STEP, __ballot(1));
     int32_t ref = leaf_member<PK>(S, lf, i);
-    renorm(w);  // _ray.getTransformedRay(_ray, obj.CTMara[invIDX])
+    renorm<KN_UNIT<F>>(w);  // _ray.getTransformedRay(_ray, obj.CTMara[invIDX])
     if constexpr (!INST && (F & FT_INST) != 0) {
       if (is_inst<F>(S, ref)) {  // a sierpinski element: myInstance.intersectCheck
         inst_closest<CNT, F>(S, ~ref, w, k, hc.top, best, local, ct);
@@ -393,7 +413,7 @@ DEVI void leaf_closest(const SceneD& S, int32_t leaf, int accXf, V ao, V ad, WRa
       th = false;
       if (!tri_f32_out(TF, trf)) {
         const TriG T = sload_tri(S.tri + ref);
-        th = tri_test(T, o, d, t, args, LimClosest{local, best.t});
+        th = tri_test<KN_SIGN<F>>(T, o, d, t, args, LimClosest{local, best.t});
       }
     } else {
       th = test_ref_u<CNT, F, PK>(S, ref, o, d, k, t, args, ct, LimClosest{local, best.t});
@@ -1067,7 +1087,7 @@ DEVI void accel_closest_nf(const SceneD& S, const AccelD& A, V ao, V ad, RayInv 
         if (need) {
           double t;
           int args;
-          const bool th = tri_test(T, ao, ad, t, args, LimNF{bt, best.t});
+          const bool th = tri_test<KN_SIGN<F>>(T, ao, ad, t, args, LimNF{bt, best.t});
           PKSTAT_HIT(P_CTH_STEP, th);
           if (th && (t < bt || (t == bt && st + i < bref))) {
             bt = t;
@@ -1318,7 +1338,7 @@ DEVI Best closest(const SceneD& S, WRay& w, const Key& k, Counters& ct) {
   for (int i = 0; i < S.ntop; ++i) {
     TopD tp = PK ? sload_top(S.top + i) : S.top[i];
     if (CNT) ct.c[C_TOP]++;
-    renorm(w);
+    renorm<KN_UNIT<F>>(w);
     if ((F & FT_INST) && tp.kind == TOP_INST) {
       double local = best.t;
       inst_closest<CNT, F>(S, tp.idx, w, k, i, best, local, ct);
@@ -1386,7 +1406,7 @@ DEVI bool leaf_any(const SceneD& S, int32_t leaf, int accXf, V ao, V ad, WRay& w
   for (int i = 0; i < lf.count; ++i) {
     if (PK) PKSTAT(P_AT_STEP, __ballot(1));
     int32_t ref = leaf_member<PK>(S, lf, i);
-    renorm(w);
+    renorm<KN_UNIT<F>>(w);
     if constexpr (!INST && (F & FT_INST) != 0) {
       if (is_inst<F>(S, ref)) {  // myInstance.calcShadowHit
         if (inst_any<CNT, F>(S, ~ref, w, k, dist, ct)) return true;
@@ -1411,7 +1431,7 @@ DEVI bool leaf_any(const SceneD& S, int32_t leaf, int accXf, V ao, V ad, WRay& w
       th = false;
       if (!tri_f32_out(TF, trf)) {
         const TriG T = sload_tri(S.tri + ref);
-        th = tri_test(T, o, d, t, args, LimShadow{dist}) && (dist - t) > EPS;
+        th = tri_test<KN_SIGN<F>>(T, o, d, t, args, LimShadow{dist}) && (dist - t) > EPS;
       }
     } else {
       th = test_ref_u<CNT, F, PK>(S, ref, o, d, k, t, args, ct, LimShadow{dist}) && (dist - t) > EPS;
@@ -1607,7 +1627,7 @@ DEVI bool shadowed_(const SceneD& S, WRay& w, const Key& k, double dist, Counter
     if (WC && i < 64) {
       const uint64_t rest = cand & (~0ull << i);
       const int nx = rest ? (int)__builtin_ctzll(rest) : S.ntop;
-      for (int j = i; j < nx && !w.stable; ++j) renorm(w);
+      for (int j = i; j < nx && !w.stable; ++j) renorm<KN_UNIT<F>>(w);
       if (nx >= S.ntop) break;
       i = nx;
     }
@@ -1626,7 +1646,7 @@ DEVI bool shadowed_(const SceneD& S, WRay& w, const Key& k, double dist, Counter
 #ifdef RT_PROF_SH_NOACCEL
     if (tp.kind == TOP_ACCEL) continue;
 #endif
-    renorm(w);
+    renorm<KN_UNIT<F>>(w);
     if ((F & FT_INST) && tp.kind == TOP_INST) {
       if (inst_any<CNT, F>(S, tp.idx, w, k, dist, ct)) return true;
       continue;
@@ -1686,8 +1706,13 @@ template <uint32_t F>
 DEVI HitRec make_hit(const SceneD& S, const Best& b, const WRay& w, const Key& k) {
   HitRec h;
   int32_t ref = b.ref;
-  V dw = w.d0;  // direction at the winning test: d0 re-normalised `ver` times
-  for (uint32_t i = 0; i < b.ver; ++i) dw = nrmz(dw);
+  // direction at the winning test: d0 re-normalised `ver` times. renorm keeps w.d == nrmz^w.ver(d0),
+  // so the ray holds that value when no later re-normalisation moved it (RT_HIT_DW=0: always recomputed)
+  V dw = w.d;
+  if (!KN_DW<F> || b.ver != w.ver) {
+    dw = w.d0;
+    for (uint32_t i = 0; i < b.ver; ++i) dw = nrmz(dw);
+  }
   int xf, xfc;
   if (!(F & FT_PRIM) || ref >= 0) { const TriD& T = S.tri[ref]; xf = T.xf; xfc = T.xfc; h.mat = T.mat; h.key = T.key; h.type = PT_TRI; }
   else { const PrimD& P = S.prim[~ref]; xf = P.xf; xfc = P.xfc; h.mat = P.mat; h.key = P.key; h.type = P.type; }
@@ -2850,6 +2875,9 @@ DEVI double pow_shade(double x, double e) {
   }
   return r;
 }
+// RT_LIGHT_DIST (default 1): for a point / spot light with the identity CTM (LightD.pad[0] == 1) the
+// shadow distance |fwd - origin| is the magnitude that normalising (origin - fwd) has just computed:
+// (a - b)^2 == (b - a)^2 exactly, summed in the same order (light_sum, shadow_ray; 0: its own sqrt)
 // STASH (packet kernels): h.nrm, h.dw and tex are in the LDS slots (shade_node), the sums too
 template <bool CNT, uint32_t F, bool STASH>
 DEVI V light_sum(const SceneD& S, const MatD& m, const HitRec& h, V tex, const Key& k, Counters& ct) {
@@ -2872,7 +2900,8 @@ DEVI V light_sum(const SceneD& S, const MatD& m, const HitRec& h, V tex, const K
     const bool disk = (F & FT_LIGHTX) && ltype == 2;
     V lo = disk ? disk_pos<(RT_ULOAD & 2) != 0>(L, k, 0) : lorg;
     V ln = xpt(lg, lo);
-    ln = nrmz(mk(ln.x - h.fwd.x, ln.y - h.fwd.y, ln.z - h.fwd.z));
+    double lm;
+    ln = nrmz_m(mk(ln.x - h.fwd.x, ln.y - h.fwd.y, ln.z - h.fwd.z), lm);
     WRay sr;
     sr.o = h.fwd;
     sr.d = nrmz(ln);  // myRay ctor normalises again
@@ -2880,8 +2909,13 @@ DEVI V light_sum(const SceneD& S, const MatD& m, const HitRec& h, V tex, const K
     sr.stable = false;
     sr.moved = false;
     sr.ver = 0;
-    V lo2 = disk ? disk_pos<(RT_ULOAD & 2) != 0>(L, k, 2) : lorg;
-    double t = sqrt((((sr.o.x - lo2.x) * (sr.o.x - lo2.x)) + ((sr.o.y - lo2.y) * (sr.o.y - lo2.y))) + ((sr.o.z - lo2.z) * (sr.o.z - lo2.z)));
+    double t;
+    if (KN_DIST<F> && sload(&L.pad[0]) == 1) {
+      t = lm;  // the light sits at lorg in world space: |fwd - lorg| is the magnitude just divided by
+    } else {
+      V lo2 = disk ? disk_pos<(RT_ULOAD & 2) != 0>(L, k, 2) : lorg;
+      t = sqrt((((sr.o.x - lo2.x) * (sr.o.x - lo2.x)) + ((sr.o.y - lo2.y) * (sr.o.y - lo2.y))) + ((sr.o.z - lo2.z) * (sr.o.z - lo2.z)));
+    }
     double ltMult = 1;
     if (CNT) ct.c[C_LIGHT]++;
     WCNT(C_WLIGHT, 1);  // the light record: scalar loads, once per wave
@@ -2901,7 +2935,7 @@ DEVI V light_sum(const SceneD& S, const MatD& m, const HitRec& h, V tex, const K
     if (false)
 #endif
     if (shadowed<CNT, F, PACKET, WAVE_CULL<F>>(S, sr, sk, t, ct, li)) continue;
-    renorm(sr);  // shadowRay.direction._normalize()
+    renorm<KN_UNIT<F>>(sr);  // shadowRay.direction._normalize()
     if (STASH) {
       if (F & FT_LIGHTX) ltMult = unstash(SL_LTM);
       const V rgb = unstash3(SL_RGB);
@@ -3386,12 +3420,17 @@ DEVI ShRay shadow_ray(const SceneD& S, int li, V fwd, const Key& k) {
   const bool disk = (F & FT_LIGHTX) && ltype == 2;
   const V lo = disk ? disk_pos<U>(L, k, 0) : lorg;
   V ln = xpt(lg, lo);
-  ln = nrmz(mk(ln.x - fwd.x, ln.y - fwd.y, ln.z - fwd.z));
+  double lm;
+  ln = nrmz_m(mk(ln.x - fwd.x, ln.y - fwd.y, ln.z - fwd.z), lm);
   ShRay r;
   r.d = nrmz(ln);  // myRay ctor normalises again
-  const V lo2 = disk ? disk_pos<U>(L, k, 2) : lorg;
-  r.dist = sqrt((((fwd.x - lo2.x) * (fwd.x - lo2.x)) + ((fwd.y - lo2.y) * (fwd.y - lo2.y))) +
-                ((fwd.z - lo2.z) * (fwd.z - lo2.z)));
+  if (KN_DIST<F> && (U ? sload(&L.pad[0]) : L.pad[0]) == 1) {
+    r.dist = lm;  // RT_LIGHT_DIST above
+  } else {
+    const V lo2 = disk ? disk_pos<U>(L, k, 2) : lorg;
+    r.dist = sqrt((((fwd.x - lo2.x) * (fwd.x - lo2.x)) + ((fwd.y - lo2.y) * (fwd.y - lo2.y))) +
+                  ((fwd.z - lo2.z) * (fwd.z - lo2.z)));
+  }
   r.ltm = 1;
   if ((F & FT_LIGHTX) && ltype == 1) {  // mySpotLight.calcT_Mult (myLight.java:77-82,159-163)
     const double angle = jf::acos(-1 * dot(r.d, pld3<U>(L.orient)));
@@ -3449,7 +3488,7 @@ DEVI V light_sum_w(const SceneD& S, bool hit, int32_t mat, const Key& k, Counter
 #else
           if (!shadowed<CNT, F, PACKET>(S, sr, sk, sh.dist, ct)) {
 #endif
-            renorm(sr);  // shadowRay.direction._normalize()
+            renorm<KN_UNIT<F>>(sr);  // shadowRay.direction._normalize()
             res = (int)sr.ver;
           }
           PROF_ADD(t_shd, R_SHADOW);

@@ -663,7 +663,8 @@ extern "C" int rt_scene_inspect_cli(const char* scene_dir, const char* cli_file,
   int64_t bytes = (int64_t)(hs.xf.size() * sizeof(XformD) + hs.tri.size() * (sizeof(TriD) + sizeof(TriF)) + hs.prim.size() * sizeof(PrimD) +
                             hs.node.size() * (sizeof(NodeD) + sizeof(NodeF)) + hs.leaf.size() * sizeof(LeafD) + hs.member.size() * 4 +
                             hs.accel.size() * sizeof(AccelD) + hs.top.size() * sizeof(TopD) + hs.mat.size() * sizeof(MatD) +
-                            hs.light.size() * sizeof(LightD) + hs.texel.size() * 4);
+                            hs.light.size() * sizeof(LightD) + hs.texel.size() * 4 +
+                            hs.tri.size() * HIT_NRM_DOUBLES * sizeof(double));  // the hit normals behind triF (rt_types.h)
   int64_t v[14] = {(int64_t)hs.top.size(), (int64_t)hs.light.size(), hs.bvhInternal, hs.bvhLeaves, hs.bvhDepth,
                    hs.bvhPrims, hs.nprims, hs.rpp, bytes, (int64_t)hs.tri.size(), 0, (int64_t)hs.mat.size(),
                    hs.photonMode, hs.photonCount};

@@ -196,6 +196,7 @@ struct SceneD {
   double photonMaxD2;
   double bg[3];
   int32_t bkgTex;
+  int32_t ntri;  // in the 4-byte hole ahead of sky: no offset moves (hit_nrm_table starts at triF + ntri)
   double sky[4];
   int32_t dof;
   double lensRadius, lensFocal;
@@ -208,6 +209,16 @@ struct SceneD {
   int32_t fastSlab;
 };
 enum : int32_t { SCENE_FAST_SLAB = 1, SCENE_NEAREST_FIRST = 2, SCENE_WAVE_CULL = 4 };
+// The kernels' argument layout is pinned: a field that moved the scalar loads of SceneD cost C4 6 %
+// once. New per-scene data goes into a hole or behind an existing
+// allocation (topBound's planes, triF's hit normals).
+static_assert(sizeof(SceneD) == 280 && __builtin_offsetof(SceneD, fastSlab) == 276 && __builtin_offsetof(SceneD, sky) == 216 &&
+              __builtin_offsetof(SceneD, ntri) == 212, "SceneD's layout is part of the kernels' ABI");
+// Upload-time table behind the triF allocation (trace.hip hit_tables_kernel): the hit normals,
+// double[ntri][2][3] at triF + ntri, make_hit's h.nrm of a triangle hit for orientation A and B:
+// nrmz(xvec(M.adj, nrmz(+-n))) with M = the accel CTM x own CTM (xfc >= 0) or the own CTM
+static constexpr int HIT_NRM_DOUBLES = 6;
+static_assert(sizeof(TriF) % 16 == 0, "the table behind the TriF records stays 16-B aligned");
 
 struct ParamsD {
   int32_t W, H, spp, row0, nrows, rowStep;

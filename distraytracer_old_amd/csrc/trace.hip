@@ -41,18 +41,44 @@ static const int H_PERM[256] = {151,160,137,91,90,15,131,13,201,95,96,53,194,233
   215,61,156,180};
 static const int H_GRAD3[12][3] = {{1,1,0},{-1,1,0},{1,-1,0},{-1,-1,0},{1,0,1},{-1,0,1},{1,0,-1},{-1,0,-1},{0,1,1},{0,-1,1},{0,1,-1},{0,-1,-1}};
 
+// `tail`: bytes allocated behind the records for a table a device kernel fills (hit_tables_kernel)
 template <class T>
-static int upload(rt_scene* s, const std::vector<T>& v, const T** out) {
+static int upload(rt_scene* s, const std::vector<T>& v, const T** out, size_t tail = 0) {
   if (v.empty()) { *out = nullptr; return RT_OK; }
   void* p = nullptr;
   size_t bytes = v.size() * sizeof(T);
-  HIPCHK(hipMalloc(&p, bytes));
+  HIPCHK(hipMalloc(&p, bytes + tail));
   s->allocs.push_back(p);
-  s->devBytes += bytes;
+  s->devBytes += bytes + tail;
   HIPCHK(hipMemcpy(p, v.data(), bytes, hipMemcpyHostToDevice));
   *out = (const T*)p;
   return RT_OK;
 }
+
+// The upload-time hit normals (rt_types.h): thread i < ntri writes triangle i's world normal for both
+// orientations with the functions and the operand order of the statements they stand for
+// (trace_kernels.h make_hit), so an entry equals what those compute, NaNs of a singular CTM
+// included. Orientation B is stored, not negated from A: xvec sums from +0.0, so a component that
+// is exactly zero is +0 in both.
+static constexpr int HIT_TABLES_BLOCK = 256;
+namespace rt {
+namespace dv {
+__global__ void __launch_bounds__(HIT_TABLES_BLOCK) hit_tables_kernel(SceneD S, double* __restrict__ nrm) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= S.ntri) return;
+  const TriD& T = S.tri[i];
+  const XformD& M = S.xf[T.xfc >= 0 ? T.xfc : T.xf];
+  const V nA = ld3(T.n);
+  for (int args = 0; args < 2; ++args) {
+    V n = args ? mk(-nA.x, -nA.y, -nA.z) : nA;
+    n = nrmz(n);
+    const V w = nrmz(xvec(M.adj, n));
+    double* o = nrm + ((long)i * HIT_NRM_DOUBLES + args * 3);
+    o[0] = w.x; o[1] = w.y; o[2] = w.z;
+  }
+}
+}  // namespace dv
+}  // namespace rt
 
 // Conservative world-space bounds used to skip top-level entries a ray cannot hit
 // (closest() / shadowed(), trace_kernels.h top_culled):
@@ -300,7 +326,8 @@ static int upload_scene(rt_scene* s) {
       r.pad[0] = r.pad[1] = 0;
       if (!std::isfinite(r.tm)) r.k = INFINITY;
     }
-    if ((rc = upload(s, tf, &d.triF))) return rc;
+    if ((rc = upload(s, tf, &d.triF, tf.size() * HIT_NRM_DOUBLES * sizeof(double)))) return rc;
+    d.ntri = (int)h.tri.size();
   }
   d.triUV = nullptr;
   {  // triangle UVs only matter for image-textured triangles
@@ -346,6 +373,12 @@ static int upload_scene(rt_scene* s) {
   d.fastSlab = ok ? SCENE_FAST_SLAB : 0;
   HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(dv::c_perm), H_PERM, sizeof(H_PERM)));
   HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(dv::c_grad3), H_GRAD3, sizeof(H_GRAD3)));
+  if (d.ntri) {  // after the uploads the kernel reads: tri, xf
+    hipLaunchKernelGGL(dv::hit_tables_kernel, dim3((unsigned)((d.ntri + HIT_TABLES_BLOCK - 1) / HIT_TABLES_BLOCK)), dim3(HIT_TABLES_BLOCK), 0, 0, d,
+                       const_cast<double*>(reinterpret_cast<const double*>(d.triF + d.ntri)));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+  }
   void* cnt = nullptr;
   HIPCHK(hipMalloc(&cnt, sizeof(unsigned long long) * RT_ST_N));
   s->allocs.push_back(cnt);

@@ -52,6 +52,14 @@ template <uint32_t F> static constexpr bool KN_UNIT = RT_RENORM_UNIT != 0 && kno
 template <uint32_t F> static constexpr bool KN_SIGN = RT_PLANAR_SIGN != 0 && known_norm<F>();
 template <uint32_t F> static constexpr bool KN_DW = RT_HIT_DW != 0 && known_norm<F>();
 template <uint32_t F> static constexpr bool KN_DIST = RT_LIGHT_DIST != 0 && known_norm<F>();
+// RT_HIT_NRM (default 1, the same variants): make_hit reads a triangle hit's world normal from the
+// upload-time table (rt_types.h). trace.hip's hit_tables_kernel fills it with this file's own
+// functions, so an entry is the value the statements it replaces compute, bit for bit.
+#ifndef RT_HIT_NRM
+#define RT_HIT_NRM 1
+#endif
+template <uint32_t F> static constexpr bool KN_NRM = RT_HIT_NRM != 0 && known_norm<F>();
+DEVI const double* hit_nrm_table(const SceneD& S) { return reinterpret_cast<const double*>(S.triF + S.ntri); }
 
 static __constant__ int c_perm[256];  // one copy per translation unit (trace.hip uploads its own)
 static __constant__ int c_grad3[12][3];
@@ -1749,7 +1757,14 @@ DEVI HitRec make_hit(const SceneD& S, const Best& b, const WRay& w, const Key& k
   V p = mk(trd.x * t + tro.x, trd.y * t + tro.y, trd.z * t + tro.z);
   h.hitLoc = p;
   V n;
-  if (!(F & FT_PRIM) || ref >= 0) {  // planar getNormalAtPoint: the stored N, normalised again
+  // RT_HIT_NRM: h.nrm of a triangle hit depends on (triangle, orientation) alone once M is the CTM
+  // the table was built with: xfc for an accel member, the own CTM otherwise. A triangle that is both a
+  // top-level entry and an accel member (the descriptor API allows it) is hit with inAcc == 0 and
+  // xfc >= 0: it and every instance hit take the statements below.
+  bool tab = false;
+  if constexpr (KN_NRM<F>) tab = !((F & FT_INST) && b.inst >= 0) && ((b.inAcc != 0) == (xfc >= 0));
+  if (tab) {  // no object-space normal: the table entry is read below, as late as it can be
+  } else if (!(F & FT_PRIM) || ref >= 0) {  // planar getNormalAtPoint: the stored N, normalised again
     V nA = ld3(S.tri[ref].n);
     n = args ? mk(-nA.x, -nA.y, -nA.z) : nA;
     n = nrmz(n);
@@ -1785,7 +1800,8 @@ DEVI HitRec make_hit(const SceneD& S, const Best& b, const WRay& w, const Key& k
   }
   const XformD& M = (hitXf >= 0) ? S.xf[hitXf] : (b.inAcc && xfc >= 0) ? S.xf[xfc] : X;  // Q4: accel CTM x object CTM
   h.fwd = xpt(M.g, p);
-  h.nrm = nrmz(xvec(M.adj, n));
+  if (tab) h.nrm = ld3(hit_nrm_table(S) + ((long)ref * HIT_NRM_DOUBLES + args * 3));
+  else h.nrm = nrmz(xvec(M.adj, n));
   h.dw = ((F & FT_PRIM) && h.type == PT_BOX) ? xvec(X.g, trd) : dw;
   return h;
 }

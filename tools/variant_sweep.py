@@ -168,6 +168,7 @@ VARIANTS = {  # name -> -D defines; names like "s12w4" are parsed (see defines_o
     # known normalisations: each part off, and all four off (the statements as they were)
     "ru0": ["RT_RENORM_UNIT=0"], "dw0": ["RT_HIT_DW=0"], "ld0": ["RT_LIGHT_DIST=0"], "ps0": ["RT_PLANAR_SIGN=0"],
     "kn0": ["RT_RENORM_UNIT=0", "RT_HIT_DW=0", "RT_LIGHT_DIST=0", "RT_PLANAR_SIGN=0"],
+    "hn0": ["RT_HIT_NRM=0"],                  # hit normals computed per hit, not read from the upload-time table
     "c4mr": ["@trace.hip:-Xarch_device", "@trace.hip:-mllvm=--amdgpu-sched-strategy=iterative-minreg",
              "@trace.hip:-Xarch_device", "@trace.hip:-mllvm=--amdgpu-use-amdgpu-trackers=1"],
 }

@@ -231,12 +231,11 @@ DEVI int slab_apx(const double* mn, const double* mx, V o, const double* y, doub
   if (-diff > tol) return 0;
   return -1;
 }
-// The same approximate test as two masks instead of a tri-state int (RT_APX2): `sure` -- the box
-// decision is settled (a miss, or a hit / miss beyond the margin); the return value -- a settled hit.
-// The compares feed the branch as lane masks; the int's selects and re-compares are gone.
-#ifndef RT_APX2
-#define RT_APX2 0
-#endif
+// The same approximate test as two masks instead of a tri-state int: `sure` -- the box decision is
+// settled (a miss, or a hit / miss beyond the margin); the return value -- a settled hit. The
+// compares feed the branch as lane masks; the int's selects and re-compares are gone. The box tests
+// below take it where their caller asks (A2: the packet traversals of the variants without
+// transparent materials, trace_kernels.h MASKOPS).
 DEVI bool slab_apx2(const double* mn, const double* mx, V o, const double* y, double& lo, bool& sure) {
   const double b0 = mn[0], b1 = mn[1], b2 = mn[2], b3 = mx[0], b4 = mx[1], b5 = mx[2];
   const double t0 = (b0 - o.x) * y[0], t3 = (b3 - o.x) * y[0];
@@ -255,7 +254,7 @@ DEVI bool slab_exact(const double* mn, const double* mx, V o, V d, const RayInv&
   return slab_t<false>(mn, mx, o, d, nullptr, tEntry);
 }
 // hit?  (myBBox.intersectCheck != null)
-template <bool A2 = (RT_APX2 != 0)>  // A2: slab_apx2 (lane masks)
+template <bool A2>  // A2: slab_apx2 (lane masks)
 DEVI bool box_hit(const double* mn, const double* mx, V o, V d, const RayInv& ri) {
   double te;
   if (A2 && ri.fast) {
@@ -269,7 +268,7 @@ DEVI bool box_hit(const double* mn, const double* mx, V o, V d, const RayInv& ri
   return slab_exact(mn, mx, o, d, ri, te);
 }
 // hit and (lim == DMAX or entry t < lim)   (BVH right-child rule)
-template <bool A2 = (RT_APX2 != 0)>  // A2: slab_apx2 (lane masks)
+template <bool A2>  // A2: slab_apx2 (lane masks)
 DEVI bool box_before(const double* mn, const double* mx, V o, V d, const RayInv& ri, double lim) {
   double te;
   if (A2 && ri.fast) {
@@ -296,7 +295,7 @@ DEVI bool box_before(const double* mn, const double* mx, V o, V d, const RayInv&
   return lim == DMAX || te < lim;
 }
 // hit and dist - entry t > 1e-7   (calcShadowHit on a box)
-template <bool A2 = (RT_APX2 != 0)>  // A2: slab_apx2 (lane masks)
+template <bool A2>  // A2: slab_apx2 (lane masks)
 DEVI bool box_shadow(const double* mn, const double* mx, V o, V d, const RayInv& ri, double dist) {
   double te;
   if (A2 && ri.fast) {
@@ -322,7 +321,7 @@ DEVI bool box_shadow(const double* mn, const double* mx, V o, V d, const RayInv&
 
 // box_shadow that also reports the box's entry t (approximate: the ordering of the nearest-first
 // any-hit traversal, never a decision)
-template <bool A2 = (RT_APX2 != 0)>  // A2: slab_apx2 (lane masks)
+template <bool A2>  // A2: slab_apx2 (lane masks)
 DEVI bool box_shadow_e(const double* mn, const double* mx, V o, V d, const RayInv& ri, double dist, double& te) {
   if (A2 && ri.fast) {
     bool sure;

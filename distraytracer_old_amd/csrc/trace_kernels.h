@@ -1,5 +1,6 @@
 // HIP kernels (gfx950) for the reference's per-pixel / per-sample trace loop.
-// Included by trace.hip only.
+// Included by trace.hip and render_minreg.hip (the render kernels' two translation units) and, through
+// query_kernels.h and shade_kernels.h, by query.hip, ray_sort.hip and shade.hip.
 //
 // Kernel structure: one lane per pixel (8x8 pixel tiles per 64-lane wave for
 // ray coherence); per sample: camera ray -> shading tree evaluated post-order
@@ -93,19 +94,10 @@ struct HitCtx {
 // Implicit primitives at a wave-uniform address (the packet kernels' top-level scans) as scalar loads
 // into SGPRs: the record no longer occupies VGPRs inside C4's shadow scan, whose reloads of spilled
 // values in that loop went from 21 static scratch ops to 1 (C4 469.5 -> 454.4 ms, C5 195.3 -> 195.1 ms,
-// same images: profiles/r05h_sprim_ab.log). RT_SPRIM 2 = every variant, 1 = the variants without a
-// photon map, 0 = none (vector loads, one per lane)
-// RT_ULOAD: other wave-uniform records read in hot loops as scalar loads -- bit 0: a leaf member's
-// transform inverse in the packet traversals (C3 3.069 -> 3.056 ms, C4 unchanged), bit 1: the light
-// record's spot / disk fields in light_sum (C4 456 -> 476 ms: off). profiles/r05i_uload_ab.log
-#ifndef RT_ULOAD
-#define RT_ULOAD 1
-#endif
-#ifndef RT_SPRIM
-#define RT_SPRIM 2
-#endif
-template <uint32_t F>
-static constexpr bool SPRIM = RT_SPRIM == 2 || (RT_SPRIM == 1 && (F & FT_PHOTON) == 0);
+// same images: profiles/r05h_sprim_ab.log), in every variant.
+// Of the other wave-uniform records read in hot loops, a leaf member's transform inverse is read as
+// scalar loads in the packet traversals (C3 3.069 -> 3.056 ms, C4 unchanged); the light record's spot /
+// disk fields in light_sum are not (C4 456 -> 476 ms with them). profiles/r05i_uload_ab.log
 // WAVE: the record address is wave-uniform (counted once per wave step), else per lane
 template <bool CNT, uint32_t F, class LIM = LimNone, bool WAVE = false>
 DEVI bool test_ref(const SceneD& S, int32_t ref, V o, V d, const Key& k, double& t, int& args, Counters& ct,
@@ -121,7 +113,7 @@ DEVI bool test_ref(const SceneD& S, int32_t ref, V o, V d, const Key& k, double&
     ct.c[c]++;
     if (WAVE) WCNT(c + (C_WQUAD - C_QUAD), 1); else ct.c[c + (C_WQUAD - C_QUAD)]++;
   }
-  return prim_test<WAVE && SPRIM<F>>(P, o, d, k, t, args);
+  return prim_test<WAVE>(P, o, d, k, t, args);
 }
 template <uint32_t F>
 DEVI int32_t ref_xf(const SceneD& S, int32_t ref) { return (!(F & FT_PRIM) || ref >= 0) ? S.tri[ref].xf : S.prim[~ref].xf; }
@@ -184,26 +176,20 @@ DEVI int32_t uni(int32_t v) { return __builtin_amdgcn_readfirstlane(v); }
 DEVI uint64_t uni64(uint64_t v) {
   return ((uint64_t)(uint32_t)uni((int32_t)(v >> 32)) << 32) | (uint32_t)uni((int32_t)(uint32_t)v);
 }
-// this lane's bit of a wave-uniform lane mask. RT_INV_BALLOT: as the mask itself (inverse ballot: the
-// SGPR mask becomes the branch's exec / vcc mask, no per-lane shift and compare on the VALU)
-#ifndef RT_INV_BALLOT
-#define RT_INV_BALLOT 0
-#endif
-template <bool IB = (RT_INV_BALLOT != 0)>
+// this lane's bit of a wave-uniform lane mask. IB: as the mask itself (inverse ballot: the SGPR mask
+// becomes the branch's exec / vcc mask, no per-lane shift and compare on the VALU)
+template <bool IB>
 DEVI bool in_mask_t(uint64_t m) {
   if constexpr (IB) return __builtin_amdgcn_inverse_ballot_w64(m);
   else return (m >> __lane_id()) & 1;
 }
-DEVI bool in_mask(uint64_t m) { return in_mask_t<>(m); }
+DEVI bool in_mask(uint64_t m) { return in_mask_t<false>(m); }
 // MASKOPS<F>: the packet traversals' lane bits by inverse ballot and their approximate box tests as
 // lane masks (slab_apx2) -- C3 3.024 -> 2.994 ms, but C4's transparent variant 453 -> 459 ms through
 // its allocation, C5 unchanged (profiles/r05w_maskops_ab.log): on in the variants without
-// transparent materials (RT_MASKOPS 1), everywhere (2) or nowhere (0)
-#ifndef RT_MASKOPS
-#define RT_MASKOPS 1
-#endif
+// transparent materials only
 template <uint32_t F>
-static constexpr bool MASKOPS = RT_MASKOPS == 2 || (RT_MASKOPS == 1 && (F & FT_TRANS) == 0);
+static constexpr bool MASKOPS = (F & FT_TRANS) == 0;
 #ifdef RT_PROF_PKSTAT
 __device__ unsigned long long rt_pk_stat[16];
 // one wave step testing the lanes in m: counted once per wave (by its first active lane)
@@ -253,7 +239,7 @@ DEVI double opaque_d(double x) {  // kept from being hoisted out of the traversa
   return x;
 }
 
-// ---- conservative fp32 triangle pre-test (RT_F32_TRI) ------------------------------------------
+// ---- conservative fp32 triangle pre-test -------------------------------------------------------
 // Most wave steps of the packet traversals' triangle tests have no lane that hits (C3: 83 % of the
 // nearest-first closest-hit steps, 82 % of the shadow steps; profiles/r06v_pkstat_c3.json), yet each
 // runs the fp64 test with its IEEE division (planar_test; myPlanarObject.java:165-211). A lane is
@@ -270,22 +256,11 @@ DEVI double opaque_d(double x) {  // kept from being hoisted out of the traversa
 // that edge whatever its t -- the lane's result is false, which is all the pre-test ever decides.
 // It decides nothing where s' is within its rounding of 0 (the sign of s could differ) or B is large
 // enough for a product to overflow; a non-finite record has k = +inf (B = +inf or NaN: no compare holds).
-#ifndef RT_F32_TRI
-#define RT_F32_TRI 1
-#endif
-#ifndef RT_F32_TRI_CPK  // ... in the reference-order closest hit (leaf_closest) too
-#define RT_F32_TRI_CPK 1
-#endif
-// Measured (same-box A/Bs, same image hashes): C3 2.867 -> 2.824 ms (nearest-first closest hit + shadow
-// rays), C4 489 -> 465 ms (+ the reference-order closest hit: 489 without it); the photon-map variant
-// loses with it in either traversal (C5 173.0 ms without, 175.6 / 175.1 ms with it in the closest hit /
-// both), so it is off there (profiles/r06w_*, r06y_f32_tri_ab.log, r06z_f32_tri_photon_ab.log)
-#ifndef RT_F32_TRI_PH_ANY  // ... in the photon-map variant's shadow rays
-#define RT_F32_TRI_PH_ANY 0
-#endif
-#ifndef RT_F32_TRI_PH_CPK  // ... in the photon-map variant's closest hit
-#define RT_F32_TRI_PH_CPK 0
-#endif
+// It runs in the nearest-first closest hit, the shadow rays and the reference-order closest hit
+// (leaf_closest). Measured (same-box A/Bs, same image hashes): C3 2.867 -> 2.824 ms (nearest-first
+// closest hit + shadow rays), C4 489 -> 465 ms (+ the reference-order closest hit: 489 without it); the
+// photon-map variant loses with it in either traversal (C5 173.0 ms without, 175.6 / 175.1 ms with it in
+// the closest hit / both), so it has none (profiles/r06w_*, r06y_f32_tri_ab.log, r06z_f32_tri_photon_ab.log)
 struct TriRayF {
   float o[3], d[3];
   float O, D;  // |o'|_1, |d'|_1
@@ -388,9 +363,8 @@ DEVI void leaf_closest(const SceneD& S, int32_t leaf, int accXf, V ao, V ad, WRa
                        Best& best, double& local, Counters& ct) {
   const LeafR lf = leaf_of<PK>(S, leaf);
   if (CNT) { ct.c[C_LEAF]++; ct.c[C_MEMBER] += lf.count; }
-  // the fp32 triangle pre-test (members in the accel's CTM; RT_F32_TRI_CPK)
-  constexpr bool TF32 = PK && !INST && RT_F32_TRI != 0 && RT_F32_TRI_CPK != 0 &&
-                        ((F & FT_PHOTON) == 0 || RT_F32_TRI_PH_CPK != 0);
+  // the fp32 triangle pre-test (members in the accel's CTM)
+  constexpr bool TF32 = PK && !INST && (F & FT_PHOTON) == 0;
   TriRayF trf;
   if constexpr (TF32) trf = tri_ray_f32(ao, ad);
   for (int i = 0; i < lf.count; ++i) {
@@ -406,7 +380,7 @@ DEVI void leaf_closest(const SceneD& S, int32_t leaf, int accXf, V ao, V ad, WRa
     int xf = ref_xf_u<F, PK>(S, ref);
     V o, d;
     if (xf == accXf && !w.moved) { o = ao; d = ad; }
-    else if (PK && (RT_ULOAD & 1)) {  // xf is wave-uniform here (ref_xf_u): the inverse as scalar loads
+    else if (PK) {  // xf is wave-uniform here (ref_xf_u): the inverse as scalar loads
       double inv[12];
       sload_inv(S.xf + xf, inv);
       o = xpt(inv, w.o); d = xvec(inv, w.d);
@@ -603,13 +577,10 @@ DEVI void stash(int q, double v) { pkT()[q * 64 + __lane_id()] = v; }
 // A wave-uniform value (kernel argument, in SGPRs) made opaque where it is used: what is derived
 // from it (its copy into VGPRs, a conversion) is then computed at the use instead of being hoisted
 // out of the sample loop and spilled to scratch across the shading tree -- a per-wave store of 64
-// copies of the same value (RT_UNI_OPAQUE; C3 wrote ~4 KB per wave that way at the loop's entry)
-#ifndef RT_UNI_OPAQUE
-#define RT_UNI_OPAQUE 1
-#endif
+// copies of the same value (C3 wrote ~4 KB per wave that way at the loop's entry)
 template <class T>
 DEVI T uni_here(T v) {
-  if (RT_UNI_OPAQUE) asm volatile("" : "+s"(v));
+  asm volatile("" : "+s"(v));
   return v;
 }
 DEVI double unstash(int q) { return pkT()[q * 64 + __lane_id()]; }
@@ -643,7 +614,7 @@ struct PkStack {
   DEVI int32_t getC(int i) const { return uni(pkC()[i]); }
 };
 
-// ---- conservative fp32 box pre-test (RT_F32_BOX) ---------------------------------------------
+// ---- conservative fp32 box pre-test ----------------------------------------------------------
 // The packet traversals' child-box tests first run in fp32 on the node's fp32 boxes (NodeF): a
 // wave64 f32 fma / add / min is issued at twice the rate of its fp64 form on gfx950, and the whole
 // test is ~22 instructions instead of ~30 fp64 ones (tools/valu_issue.hip). A decision
@@ -656,24 +627,12 @@ struct PkStack {
 // 2^-24 of values <= 2^20 E: a miss is certain when hi' < lo' - 4E or lo' < -2E, a hit when
 // hi' > lo' + 4E and lo' > 2E (the reference's own rounding, ~2^-51 relative, is far inside these
 // margins). Overflow makes E (and the test) +inf or NaN: nothing is settled then.
-#ifndef RT_F32_BOX
-#define RT_F32_BOX 1
-#endif
-// In the shadow (any-hit) packet traversal: C4 482 -> 453 ms, C5 175.1 -> 173.4 ms; in C3's
-// triangles-only variant only with the fp32 ray rebuilt per node from the fp64 one (RT_F32_SH_LAZY:
-// held through the traversal its registers made the shading code spill, 2.90 -> 2.96 ms; rebuilt,
-// 2.90 -> 2.87 ms, and C4 453 -> 450 ms; the photon variant keeps it held, C5 173.3 vs 174.6 ms).
+// In the shadow (any-hit) packet traversal of every variant: C4 482 -> 453 ms, C5 175.1 -> 173.4 ms; in
+// C3's triangles-only variant only with the fp32 ray rebuilt per node from the fp64 one (held through
+// the traversal its registers made the shading code spill, 2.90 -> 2.96 ms; rebuilt, 2.90 -> 2.87 ms,
+// and C4 453 -> 450 ms; the photon variant keeps it held, C5 173.3 vs 174.6 ms).
 // The nearest-first closest hit gains in C3 (2.94 -> 2.90 ms). Same images (profiles/r06f_f32_ab.log,
 // r06h_f32_ab_same_box.log, r06j_f32_lazy_ab.log).
-#ifndef RT_F32_SHADOW  // the fp32 pre-test in the shadow (any-hit) packet traversal
-#define RT_F32_SHADOW 1
-#endif
-#ifndef RT_F32_SHADOW_TRANS  // ... of the transparent variants
-#define RT_F32_SHADOW_TRANS 1
-#endif
-#ifndef RT_F32_SHADOW_OPAQUE  // ... of the other variants (with the fp32 ray rebuilt per node, RT_F32_SH_LAZY)
-#define RT_F32_SHADOW_OPAQUE 1
-#endif
 struct RayF {
   float y[3], noy[3];  // RN(y_i), RN(-RN(o_i) RN(y_i))
   float ymax, omax;    // >= max |y_i|, >= max |o_i|
@@ -687,7 +646,7 @@ DEVI RayF ray_f32(V o, const RayInv& ri, double ymax) {
   r.omax = (float)(fmax(fmax(fabs(o.x), fabs(o.y)), fabs(o.z)) * (1 + 0x1p-20));
   return r;
 }
-// the per-axis part of ray_f32 alone (RT_F32_SH_LAZY)
+// the per-axis part of ray_f32 alone (the fp32 ray rebuilt per node)
 DEVI RayF ray_f32_dirs(V o, const RayInv& ri) {
   RayF r;
   const float ox = (float)opaque_d(o.x), oy = (float)opaque_d(o.y), oz = (float)opaque_d(o.z);
@@ -696,18 +655,9 @@ DEVI RayF ray_f32_dirs(V o, const RayInv& ri) {
   r.ymax = r.omax = 0;
   return r;
 }
-// The same pre-test in the reference-order closest hit of the transparent variants (RT_F32_CPK) does
-// not pay: C4 450.8 -> 451.9 ms, C5 173.1 -> 175.8 ms (profiles/r06n_f32_cpk_ab.log) -- those
-// traversals test one box per step and the fp64 box's SGPRs were already loaded; off.
-#ifndef RT_F32_CPK  // the fp32 pre-test in the reference-order closest hit of the transparent variants
-#define RT_F32_CPK 0
-#endif
-#ifndef RT_F32_CPK_PHOTON  // ... of the photon-map variant too
-#define RT_F32_CPK_PHOTON 1
-#endif
-#ifndef RT_F32_SH_LAZY  // (variants without a photon map)
-#define RT_F32_SH_LAZY 1
-#endif
+// The same pre-test in the reference-order closest hit of the transparent variants does not pay:
+// C4 450.8 -> 451.9 ms, C5 173.1 -> 175.8 ms (profiles/r06n_f32_cpk_ab.log) -- those traversals test
+// one box per step and the fp64 box's SGPRs were already loaded; accel_closest_pk has none.
 DEVI float f32_margin(const RayF& r, float mag) { return 0x1p-20f * (r.ymax * (mag + r.omax)); }
 enum : int { B32_MISS = 0, B32_HIT = 1, B32_OPEN = 2 };
 // b: min[3] max[3] of one child (fp32); lo: the fp32 entry (a settled hit's entry within E)
@@ -748,20 +698,6 @@ DEVI void accel_closest_pk(const SceneD& S, const AccelD& A, V ao, V ad, RayInv 
   uint64_t act = __ballot(1);  // lanes in the current subtree
   int32_t N = uni(A.root);
   const int32_t axf = A.xf;
-  // the fp32 box pre-test (box32) in the transparent variants, whose closest hit takes this
-  // reference-order traversal (not C3's, where it is only the fat-edge fallback)
-  constexpr bool F32 = RT_F32_BOX && RT_F32_CPK && (F & FT_TRANS) != 0 && (RT_F32_CPK_PHOTON || (F & FT_PHOTON) == 0);
-  constexpr bool LAZY = RT_F32_SH_LAZY != 0 && (F & FT_PHOTON) == 0;
-  const bool f32 = F32 && ri.fast;
-  RayF rf;
-  if constexpr (F32) rf = ray_f32(ao, ri, fmax(fmax(fabs(ri.y[0]), fabs(ri.y[1])), fabs(ri.y[2])));
-  auto rebuild = [&]() {
-    if constexpr (F32 && LAZY) {
-      const RayF r2 = ray_f32_dirs(ao, ri);
-      rf.y[0] = r2.y[0]; rf.y[1] = r2.y[1]; rf.y[2] = r2.y[2];
-      rf.noy[0] = r2.noy[0]; rf.noy[1] = r2.noy[1]; rf.noy[2] = r2.noy[2];
-    }
-  };
   while (true) {
     // descend: push N, go left with the lanes whose left box is hit
     while (N >= 0) {
@@ -769,46 +705,16 @@ DEVI void accel_closest_pk(const SceneD& S, const AccelD& A, V ao, V ad, RayInv 
       PKSTAT(P_CB_STEP, act);
       WCNT(C_WNODE, 1);  // the node's record: left half now, right half at the unwind
       bool hl = false;
-      int32_t lref;
-      if constexpr (F32) {
-        const NodeD* nd = S.node + N;
-        lref = sload_ref(nd, 0);
-        bool open = false;
-        if (in_mask_t<MASKOPS<F>>(act)) {
-          if (CNT) { ct.c[C_NODE]++; ct.c[C_BOX] += 2; }
-          st.setT(sp, local);
-          local = DMAX;
-          if (f32) {
-            rebuild();
-            float b[6], mag;
-#pragma unroll
-            for (int i = 0; i < 6; ++i) b[i] = sload(S.nodeF[N].b + i);
-            mag = sload(&S.nodeF[N].mag);
-            float lo;
-            const int c = box32(b, rf, f32_margin(rf, mag), lo);
-            hl = c == B32_HIT;
-            open = c == B32_OPEN;
-          } else {
-            open = true;
-          }
-        }
-        if (__ballot(open)) {
-          const ChildBox cl = sload_child(nd, 0);
-          if (open) hl = box_hit<MASKOPS<F>>(cl.mn, cl.mx, ao, ad, ri);
-        }
-      } else {
-        const ChildBox cl = sload_child(S.node + N, 0);
-        lref = cl.ref;
-        if (in_mask_t<MASKOPS<F>>(act)) {
-          if (CNT) { ct.c[C_NODE]++; ct.c[C_BOX] += 2; }
-          st.setT(sp, local);
-          local = DMAX;
-          hl = box_hit<MASKOPS<F>>(cl.mn, cl.mx, ao, ad, ri);
-        }
+      const ChildBox cl = sload_child(S.node + N, 0);
+      if (in_mask_t<MASKOPS<F>>(act)) {
+        if (CNT) { ct.c[C_NODE]++; ct.c[C_BOX] += 2; }
+        st.setT(sp, local);
+        local = DMAX;
+        hl = box_hit<MASKOPS<F>>(cl.mn, cl.mx, ao, ad, ri);
       }
       sp++;
       const uint64_t H = __ballot(hl);
-      if (H) { act = H; N = lref; }
+      if (H) { act = H; N = cl.ref; }
       else { N = INT32_MAX; break; }
     }
     if (N != INT32_MAX && in_mask_t<MASKOPS<F>>(act)) leaf_closest<CNT, F, false, true>(S, ~N, axf, ao, ad, w, k, hc, best, local, ct);
@@ -820,47 +726,13 @@ DEVI void accel_closest_pk(const SceneD& S, const AccelD& A, V ao, V ad, RayInv 
       if ((np & 1) == 0) {
         PKSTAT(P_CB_STEP, M);
         bool gr = false;
-        int32_t rref;
-        if constexpr (F32) {
-          // hit and (local == DMAX or entry < local): settled when the entry is clear of local
-          const NodeD* nd = S.node + (np >> 1);
-          rref = sload_ref(nd, 1);
-          bool open = false;
-          if (in_mask_t<MASKOPS<F>>(M)) {
-            if (f32) {
-              rebuild();
-              float b[6], mag;
-#pragma unroll
-              for (int i = 0; i < 6; ++i) b[i] = sload(S.nodeF[np >> 1].b + 6 + i);
-              mag = sload(&S.nodeF[np >> 1].mag);
-              float lo;
-              const float E = f32_margin(rf, mag);
-              const int c = box32(b, rf, E, lo);
-              if (c == B32_HIT) {
-                const double lt = fabs(local) * 0x1p-40;
-                if (local == DMAX || (double)(lo + 2 * E) < local - lt) gr = true;
-                else if (!((double)(lo - 2 * E) > local + lt)) open = true;
-              } else {
-                open = c == B32_OPEN;
-              }
-            } else {
-              open = true;
-            }
-          }
-          if (__ballot(open)) {
-            const ChildBox cr = sload_child(nd, 1);
-            if (open) gr = box_before<MASKOPS<F>>(cr.mn, cr.mx, ao, ad, ri, local);
-          }
-        } else {
-          const ChildBox cr = sload_child(S.node + (np >> 1), 1);
-          rref = cr.ref;
-          if (in_mask_t<MASKOPS<F>>(M)) gr = box_before<MASKOPS<F>>(cr.mn, cr.mx, ao, ad, ri, local);
-        }
+        const ChildBox cr = sload_child(S.node + (np >> 1), 1);
+        if (in_mask_t<MASKOPS<F>>(M)) gr = box_before<MASKOPS<F>>(cr.mn, cr.mx, ao, ad, ri, local);
         const uint64_t R = __ballot(gr);
         if (R) {
           st.setN(sp - 1, np | 1);
           act = R;
-          N = rref;
+          N = cr.ref;
           break;
         }
       }
@@ -896,25 +768,13 @@ DEVI void accel_closest_pk(const SceneD& S, const AccelD& A, V ao, V ad, RayInv 
 // leaf box (a fat-edge hit) re-runs the reference traversal (accel_closest_pk). The image is the
 // reference's bit for bit; the counting kernel under RT_RENDER_NOCULL keeps the reference order,
 // so its counters remain the reference algorithm's.
-#ifndef RT_NEAREST_FIRST
-#define RT_NEAREST_FIRST 1
-#endif
 // The child being entered is kept as a code (node << 1 | side) and its box reloaded (scalar loads) only
 // when a lane finds a new best hit in the leaf, instead of the 13-SGPR box riding along the whole
 // traversal: at the SGPR limit it was being moved to VGPRs and spilled (C3: 3.22 -> 3.05 ms per frame,
 // scratch writes 2.30 -> 1.58 GB, reads 1.04 -> 0.67 GB; same image; profiles/r04g_*)
-#ifndef RT_NF_CODE
-#define RT_NF_CODE 1
-#endif
-#ifndef RT_NF_TRANS  // nearest-first closest hit in the transparent (non-photon) variants too
-#define RT_NF_TRANS 0
-#endif
-#ifndef RT_AN_TRANS  // nearest-first any-hit order in the transparent variants too
-#define RT_AN_TRANS 0
-#endif
-// (not in the photon-map and transparent variants, whose 128-VGPR allocation it perturbs: C5's
-// kernel lost 10 % to the unused code, C4's 3 % -- 583 -> 599 ms -- although its bunnies use it)
-static constexpr bool NEAREST_FIRST = RT_NEAREST_FIRST != 0;
+// Neither this traversal nor the nearest-first any-hit order is compiled into the photon-map and
+// transparent variants, whose 128-VGPR allocation it perturbs: C5's kernel lost 10 % to the unused
+// code, C4's 3 % -- 583 -> 599 ms -- although its bunnies use it.
 DEVI double sload_slack(const NodeD* nd, int side) {
   return sload(reinterpret_cast<const double*>(side ? &nd->padR[1] : &nd->pad[1]));
 }
@@ -928,15 +788,12 @@ DEVI double entry_grown(const double* mn, const double* mx, double s, V o, const
   const double hi = fmin(fmin(fmax(t0, t3), fmax(t1, t4)), fmax(t2, t5));
   return (hi >= lo && hi > 0) ? lo : DMAX;
 }
-// RT_NF_LB: a child's grown-box entry from its exact box's own slab values -- every axis's entry moves
+// nf_child: a child's grown-box entry from its exact box's own slab values -- every axis's entry moves
 // by at most s |y_axis| when the box grows by s, so lo - s max|y| is a lower bound of the grown entry
 // within s max|y| of it: pruning by it is conservative (it prunes no subtree the exact grown entry
 // keeps), ordering by it changes no answer (nearest-first finds h* in any order), and the box's hit
 // decision reuses the same six slab values instead of a second slab computation. C3 2.995 -> 2.926 ms,
 // same image (profiles/r05zc_c3_nf_lb_ab.log)
-#ifndef RT_NF_LB
-#define RT_NF_LB 1
-#endif
 template <bool A2>
 DEVI bool nf_child(const ChildBox& c, double s, double ymax, V o, V d, const RayInv& ri, double lim, double& e) {
   if (!ri.fast) {
@@ -974,18 +831,13 @@ DEVI void accel_closest_nf(const SceneD& S, const AccelD& A, V ao, V ad, RayInv 
   uint64_t act = __ballot(1);
   int sp = 0;
   int32_t N = uni(A.root);
-  const double ymax = fmax(fmax(fabs(ri.y[0]), fabs(ri.y[1])), fabs(ri.y[2]));  // RT_NF_LB
-  const bool f32 = RT_F32_BOX && RT_NF_LB && RT_NF_CODE && ri.fast;
+  const double ymax = fmax(fmax(fabs(ri.y[0]), fabs(ri.y[1])), fabs(ri.y[2]));  // nf_child's lower bound
+  const bool f32 = ri.fast;
   const RayF rf = ray_f32(ao, ri, ymax);
-#if RT_NF_CODE
   int32_t curCode = 0;    // the child being entered (node << 1 | side): its box is reloaded for the inside test
-#else
-  ChildBox cur;           // the box of the child being entered (a leaf's box when N < 0)
-#endif
   while (true) {
     if (N >= 0) {  // internal: both children tested now, the nearer one entered, the other pushed
       const NodeD* nd = S.node + N;
-#if RT_F32_BOX && RT_NF_LB && RT_NF_CODE
       // the fp32 pre-test on the node's 64-B fp32 record; the fp64 boxes are loaded only when a lane
       // is left unsettled (grazing rays, or a ray the pre-test cannot bound)
       const NodeBoxF nb = sload_nodef(S.nodeF + N);
@@ -1019,26 +871,6 @@ DEVI void accel_closest_nf(const SceneD& S, const AccelD& A, V ao, V ad, RayInv 
           if (orr) hr = nf_child<MASKOPS<F>>(c, sload_slack(nd, 1), ymax, ao, ad, ri, lim, er);
         }
       }
-#else
-      const ChildBox cl = sload_child(nd, 0), cr = sload_child(nd, 1);
-      const double sl = sload_slack(nd, 0), sr = sload_slack(nd, 1);
-      WCNT(C_WNODE, 1);  // a node visit (8(d) prices one at 64 B, as the reference order's)
-      bool hl = false, hr = false;
-      double el = DMAX, er = DMAX;
-      if (in_mask_t<MASKOPS<F>>(act)) {
-        if (CNT) { ct.c[C_NODE]++; ct.c[C_BOX] += 2; }
-        const double bnd = fmin(best.t, bt), lim = fmin(bnd + bnd * 0x1p-40, 0x1p1000);  // a miss (DMAX) never passes
-        if constexpr (RT_NF_LB != 0) {
-          hl = nf_child<MASKOPS<F>>(cl, sl, ymax, ao, ad, ri, lim, el);
-          hr = nf_child<MASKOPS<F>>(cr, sr, ymax, ao, ad, ri, lim, er);
-        } else {
-          el = entry_grown(cl.mn, cl.mx, sl, ao, ri.y);
-          er = entry_grown(cr.mn, cr.mx, sr, ao, ri.y);
-          if (el <= lim) hl = box_hit<MASKOPS<F>>(cl.mn, cl.mx, ao, ad, ri);
-          if (er <= lim) hr = box_hit<MASKOPS<F>>(cr.mn, cr.mx, ao, ad, ri);
-        }
-      }
-#endif
       const uint64_t L = __ballot(hl), R = __ballot(hr);
       if (L && R) {
         const int fl = (int)__builtin_ctzll(L & R);
@@ -1048,7 +880,6 @@ DEVI void accel_closest_nf(const SceneD& S, const AccelD& A, V ao, V ad, RayInv 
         pkM()[sp] = far;
         if (sp < PK_LDS && in_mask_t<MASKOPS<F>>(far)) pkT()[sp * 64 + __lane_id()] = nearLeft ? er : el;
         sp++;
-#if RT_NF_CODE
         curCode = (N << 1) | (nearLeft ? 0 : 1);
         act = nearLeft ? L : R;
         N = nearLeft ? cl.ref : cr.ref;
@@ -1060,37 +891,19 @@ DEVI void accel_closest_nf(const SceneD& S, const AccelD& A, V ao, V ad, RayInv 
         N = INT32_MAX;
       }
       if (N != INT32_MAX) continue;
-#else
-        cur = nearLeft ? cl : cr;
-        act = nearLeft ? L : R;
-      } else if (L) {
-        cur = cl; act = L;
-      } else if (R) {
-        cur = cr; act = R;
-      } else {
-        N = INT32_MAX;
-      }
-      if (N != INT32_MAX) { N = cur.ref; continue; }
-#endif
     } else {  // a leaf: a run of triangles in leaf order
       const int32_t c = ~N;
       const int32_t st = (c >> 5) & LEAF_RUN_MAXSTART, cnt = c & 31;
       if (CNT && in_mask_t<MASKOPS<F>>(act)) { ct.c[C_LEAF]++; ct.c[C_MEMBER] += cnt; }
-#if RT_F32_TRI
       const TriRayF trf = tri_ray_f32(ao, ad);
-#endif
       for (int i = 0; i < cnt; ++i) {
         PKSTAT(P_CT_STEP, act);
         WCNT(C_WTRI, 1);
         bool need = in_mask_t<MASKOPS<F>>(act);
         if (CNT && need) ct.c[C_TRI]++;
-#if RT_F32_TRI
-        {
-          const TriFR TF = sload_trif(S.triF + st + i);
-          if (need) need = !tri_f32_out(TF, trf);
-          if (!__ballot(need)) continue;
-        }
-#endif
+        const TriFR TF = sload_trif(S.triF + st + i);  // the fp32 pre-test: a wave with every lane out skips the fp64 test
+        if (need) need = !tri_f32_out(TF, trf);
+        if (!__ballot(need)) continue;
         const TriG T = sload_tri(S.tri + st + i);
         if (need) {
           double t;
@@ -1102,9 +915,7 @@ DEVI void accel_closest_nf(const SceneD& S, const AccelD& A, V ao, V ad, RayInv 
             bref = st + i;
             // the ray enters the leaf box (the reference's slab arithmetic) clearly before t
             double te;
-#if RT_NF_CODE
             const ChildBox cur = sload_child(S.node + (curCode >> 1), curCode & 1);
-#endif
             inside = slab_exact(cur.mn, cur.mx, ao, ad, ri, te) && te < t - t * 0x1p-40;
           }
         }
@@ -1130,11 +941,7 @@ DEVI void accel_closest_nf(const SceneD& S, const AccelD& A, V ao, V ad, RayInv 
         keep = e <= lim;
       }
       M = __ballot(keep);
-#if RT_NF_CODE
       if (M) { curCode = code; act = M; N = sload_ref(pn, code & 1); break; }
-#else
-      if (M) { cur = sload_child(pn, code & 1); act = M; N = cur.ref; break; }
-#endif
     }
     if (N == INT32_MAX) break;
   }
@@ -1235,16 +1042,11 @@ DEVI bool top_culled(const SceneD& S, int i, const WRay& w, double lim) {
 // entries visited change. Measured: C4 582 -> 501 ms with the spheres, 472 ms with the plane
 // sides (the per-light form 561 ms; as a real call 711-792 ms: it is inlined; the same test for
 // the closest-hit scan of a step's rays, 521 ms: dropped; profiles/r03n_*, r03o_*, r03r_*).
-#ifndef RT_WAVE_CULL
-#define RT_WAVE_CULL 1
-#endif
-// variants with the wave-level shadow cull: non-triangle primitives, no photon map (C4's); the
-// host enables it per launch (SCENE_WAVE_CULL: ntop <= 64, culling on)
-#ifndef RT_WC_TRI  // also in the triangles-only variants (C3's: two ground triangles and a BVH)
-#define RT_WC_TRI 0
-#endif
+// variants with the wave-level shadow cull: non-triangle primitives, no photon map (C4's; not the
+// triangles-only variants, C3's two ground triangles and a BVH); the host enables it per launch
+// (SCENE_WAVE_CULL: ntop <= 64, culling on)
 template <uint32_t F>
-static constexpr bool WAVE_CULL = RT_WAVE_CULL && ((F & FT_PRIM) != 0 || RT_WC_TRI) && (F & FT_PHOTON) == 0;
+static constexpr bool WAVE_CULL = (F & FT_PRIM) != 0 && (F & FT_PHOTON) == 0;
 DEVI double rdl(double v, int L) {
   const uint64_t b = __builtin_bit_cast(uint64_t, v);
   const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)b, L), hi = __builtin_amdgcn_readlane((uint32_t)(b >> 32), L);
@@ -1312,37 +1114,14 @@ DEVI void step_cands_all() {
 DEVI uint64_t step_cand(int li) { return li < GRP_MAX ? uni64(*(volatile lds_u64*)(wcM() + li)) : ~0ull; }
 
 // findClosestRayHit (myScene.java:888-903): objList scan, TreeMap keeps the first of equal t
-#ifndef RT_PACKET
-#define RT_PACKET 1
-#endif
-static constexpr bool PACKET = RT_PACKET != 0;  // render kernel: packet traversal
 // shade_node keeps the hit's normal / view direction / texture colour in the LDS slots while
-// its shadow rays are traced (stash() above); RT_STASH_SHADE=0 keeps them in registers
-#ifndef RT_STASH_SHADE
-#define RT_STASH_SHADE 1
-#endif
-static constexpr bool STASH_SHADE = PACKET && RT_STASH_SHADE != 0 && PK_LDS >= SL_N;
+// its shadow rays are traced (stash() above), given the LDS levels for them
+static constexpr bool STASH_SHADE = PK_LDS >= SL_N;
 // PK: packet traversal of the BVHs (render kernel; the lanes of a wave are coherent)
-// experiment (default off): when at least RT_LANE_DIV lanes' rays point away from the wave's first
-// ray (cosine below RT_LANE_DIV_COS), the BVHs are traversed lane by lane (accel_closest: the
-// reference order, per-lane stacks) instead of as one packet walking the union of the lanes' paths
-#ifndef RT_LANE_DIV
-#define RT_LANE_DIV 0
-#endif
-#ifndef RT_LANE_DIV_COS
-#define RT_LANE_DIV_COS 0.9
-#endif
 template <bool CNT, uint32_t F, bool PK = false>
 DEVI Best closest(const SceneD& S, WRay& w, const Key& k, Counters& ct) {
   PROF_T0(t_all);
   Best best = miss();
-  bool lanes = false;
-  if constexpr (PK && RT_LANE_DIV > 0) {
-    const int f = (int)__builtin_ctzll(__ballot(1));
-    const double c = w.d.x * rdl(w.d.x, f) + w.d.y * rdl(w.d.y, f) + w.d.z * rdl(w.d.z, f);
-    const int nfar = __popcll(__ballot(!(c >= RT_LANE_DIV_COS))), nact = __popcll(__ballot(1));
-    lanes = RT_LANE_DIV == 1 ? (nfar >= 2 && 2 * nfar >= nact) : nfar >= RT_LANE_DIV;
-  }
   for (int i = 0; i < S.ntop; ++i) {
     TopD tp = PK ? sload_top(S.top + i) : S.top[i];
     if (CNT) ct.c[C_TOP]++;
@@ -1371,9 +1150,7 @@ DEVI Best closest(const SceneD& S, WRay& w, const Key& k, Counters& ct) {
       w.moved = false;
       double local = DMAX;
       PROF_T0(t_acc);
-      if (RT_LANE_DIV > 0 && lanes)
-        accel_closest<CNT, F, false>(S, A, o, d, ri, w, k, HitCtx{i, -1, 0}, best, local, ct);
-      else if (PK && NEAREST_FIRST && (F & (FT_PHOTON | (RT_NF_TRANS ? 0 : FT_TRANS))) == 0 && (S.fastSlab & SCENE_NEAREST_FIRST) &&
+      if (PK && (F & (FT_PHOTON | FT_TRANS)) == 0 && (S.fastSlab & SCENE_NEAREST_FIRST) &&
           (A.flags & ACCEL_NEAREST) &&
           !__ballot(!(w.stable && ri.fast)))
         accel_closest_nf<CNT, F>(S, A, o, d, ri, w, k, HitCtx{i, -1, 0}, best, local, ct);
@@ -1395,7 +1172,7 @@ DEVI Best closest(const SceneD& S, WRay& w, const Key& k, Counters& ct) {
 
 // any-hit: mySceneObject/myBBox/myGeomList/myBVH.calcShadowHit (mySceneObject.java:33-38,
 // myGeomBase.java:166-170, 268-277, 397-404): blocked iff hit && dist - t > 1e-7
-template <bool CNT, bool A2 = (RT_APX2 != 0)>
+template <bool CNT, bool A2 = false>
 DEVI bool shadow_box(const double* mn, const double* mx, V o, V d, const RayInv& ri, double dist, Counters& ct) {
   if (CNT) ct.c[C_BOX]++;
   return box_shadow<A2>(mn, mx, o, d, ri, dist);
@@ -1408,7 +1185,7 @@ DEVI bool leaf_any(const SceneD& S, int32_t leaf, int accXf, V ao, V ad, WRay& w
   const LeafR lf = leaf_of<PK>(S, leaf);
   if (CNT) { ct.c[C_LEAF]++; ct.c[C_MEMBER] += lf.count; }
   // the fp32 triangle pre-test (members in the accel's CTM)
-  constexpr bool TF32 = PK && RT_F32_TRI != 0 && ((F & FT_PHOTON) == 0 || RT_F32_TRI_PH_ANY != 0);
+  constexpr bool TF32 = PK && (F & FT_PHOTON) == 0;
   TriRayF trf;
   if constexpr (TF32) trf = tri_ray_f32(ao, ad);
   for (int i = 0; i < lf.count; ++i) {
@@ -1424,7 +1201,7 @@ DEVI bool leaf_any(const SceneD& S, int32_t leaf, int accXf, V ao, V ad, WRay& w
     int xf = ref_xf_u<F, PK>(S, ref);
     V o, d;
     if (xf == accXf && !w.moved) { o = ao; d = ad; }
-    else if (PK && (RT_ULOAD & 1)) {  // xf is wave-uniform here (ref_xf_u): the inverse as scalar loads
+    else if (PK) {  // xf is wave-uniform here (ref_xf_u): the inverse as scalar loads
       double inv[12];
       sload_inv(S.xf + xf, inv);
       o = xpt(inv, w.o); d = xvec(inv, w.d);
@@ -1482,33 +1259,21 @@ DEVI bool accel_any(const SceneD& S, const AccelD& A, V ao, V ad, WRay& w, const
 // the right child, the lanes in the node's subtree (M) and those whose right box is hit
 // (R); at the unwind the lanes still unblocked in R descend. The counting kernel counts
 // the right-box test at the unwind, for the lanes in M still unblocked, as accel_any does.
-// Nearest-first (RT_ANY_NEAR, rays the re-normalisation no longer changes): when both child
+// Nearest-first (rays the re-normalisation no longer changes): when both child
 // boxes are hit, the child the ray enters first is visited first. Whether a shadow ray is blocked
 // does not depend on the order the reachable leaves are tested in (a stable ray's direction no
 // longer changes), so only the work to the first blocker changes.
-#ifndef RT_ANY_NEAR
-#define RT_ANY_NEAR 1
-#endif
 template <bool CNT, uint32_t F>
 DEVI bool accel_any_pk(const SceneD& S, const AccelD& A, V ao, V ad, WRay& w, const Key& k, double dist, Counters& ct) {
   const RayInv ri = ray_inv(ao, ad, S.fastSlab & SCENE_FAST_SLAB);
   // (C3's triangles-only variant gains 2 %; the transparent variants lose as much: not there)
-  const bool nearf = RT_ANY_NEAR && (RT_AN_TRANS || (F & FT_TRANS) == 0) && (S.fastSlab & SCENE_NEAREST_FIRST) && !__ballot(!w.stable);
+  const bool nearf = (F & FT_TRANS) == 0 && (S.fastSlab & SCENE_NEAREST_FIRST) && !__ballot(!w.stable);
   // the fp32 box pre-test (box32): a shadow box decision -- hit and (dist - entry) - EPS > 0 -- is
   // settled when the entry is certain to lie clear of dist - EPS (bracketed here by 2^-20 of it)
-  constexpr bool F32 = RT_F32_BOX && RT_F32_SHADOW && ((F & FT_TRANS) != 0 ? RT_F32_SHADOW_TRANS : RT_F32_SHADOW_OPAQUE);
-  const bool f32 = F32 && ri.fast;
-  // RT_F32_SH_LAZY: only the margin's two ray terms and the distance bracket live across the
-  // traversal; the fp32 ray itself is rebuilt from the fp64 one (live anyway) at each node -- fewer
-  // registers held through the shading code the traversal is inlined into
-  RayF rf;
-  float dLo = 0, dHi = 0;
-  if constexpr (F32) {
-    rf = ray_f32(ao, ri, fmax(fmax(fabs(ri.y[0]), fabs(ri.y[1])), fabs(ri.y[2])));
-    const double dm = dist - EPS;
-    dLo = (float)(dm - fabs(dm) * 0x1p-20);
-    dHi = (float)(dm + fabs(dm) * 0x1p-20);
-  }
+  const bool f32 = ri.fast;
+  RayF rf = ray_f32(ao, ri, fmax(fmax(fabs(ri.y[0]), fabs(ri.y[1])), fabs(ri.y[2])));
+  const double dm = dist - EPS;
+  const float dLo = (float)(dm - fabs(dm) * 0x1p-20), dHi = (float)(dm + fabs(dm) * 0x1p-20);
   PkStack st;
   int sp = 0;
   uint64_t act = __ballot(1);
@@ -1529,51 +1294,41 @@ DEVI bool accel_any_pk(const SceneD& S, const AccelD& A, V ao, V ad, WRay& w, co
       WCNT(C_WNODE, 1);
       bool hl = false, hr = false;
       double el = DMAX, er = DMAX;
-      struct { int32_t ref; } cl{0}, cr{0};
-      if constexpr (F32) {
-        const NodeD* nd = S.node + N;
-        const NodeBoxF nb = sload_nodef(S.nodeF + N);
-        cl.ref = sload_ref(nd, 0);
-        cr.ref = sload_ref(nd, 1);
-        bool ol = false, orr = false;
-        if (in_mask_t<MASKOPS<F>>(act)) {
-          if (CNT) { ct.c[C_NODE]++; ct.c[C_BOX]++; }
-          if (f32) {
-            if constexpr (RT_F32_SH_LAZY != 0 && (F & FT_PHOTON) == 0) {
-              const RayF r2 = ray_f32_dirs(ao, ri);
-              rf.y[0] = r2.y[0]; rf.y[1] = r2.y[1]; rf.y[2] = r2.y[2];
-              rf.noy[0] = r2.noy[0]; rf.noy[1] = r2.noy[1]; rf.noy[2] = r2.noy[2];
-            }
-            const float E = f32_margin(rf, nb.mag);
-            float lo;
-            const int c0 = box32(nb.b, rf, E, lo);
-            if (c0 == B32_HIT && dLo > lo + 2 * E) { hl = true; el = lo; }
-            else ol = !(c0 == B32_MISS || dHi < lo - 2 * E);
-            const int c1 = box32(nb.b + 6, rf, E, lo);
-            if (c1 == B32_HIT && dLo > lo + 2 * E) { hr = true; er = lo; }
-            else orr = !(c1 == B32_MISS || dHi < lo - 2 * E);
-          } else {
-            ol = orr = true;
+      const NodeD* nd = S.node + N;
+      const NodeBoxF nb = sload_nodef(S.nodeF + N);
+      const struct { int32_t ref; } cl{sload_ref(nd, 0)}, cr{sload_ref(nd, 1)};
+      bool ol = false, orr = false;
+      if (in_mask_t<MASKOPS<F>>(act)) {
+        if (CNT) { ct.c[C_NODE]++; ct.c[C_BOX]++; }
+        if (f32) {
+          // Without a photon map, only the margin's two ray terms (rf.ymax, rf.omax) and the distance
+          // bracket live across the traversal; the fp32 ray itself is rebuilt from the fp64 one (live
+          // anyway) at each node -- fewer registers held through the shading code the traversal is
+          // inlined into
+          if constexpr ((F & FT_PHOTON) == 0) {
+            const RayF r2 = ray_f32_dirs(ao, ri);
+            rf.y[0] = r2.y[0]; rf.y[1] = r2.y[1]; rf.y[2] = r2.y[2];
+            rf.noy[0] = r2.noy[0]; rf.noy[1] = r2.noy[1]; rf.noy[2] = r2.noy[2];
           }
+          const float E = f32_margin(rf, nb.mag);
+          float lo;
+          const int c0 = box32(nb.b, rf, E, lo);
+          if (c0 == B32_HIT && dLo > lo + 2 * E) { hl = true; el = lo; }
+          else ol = !(c0 == B32_MISS || dHi < lo - 2 * E);
+          const int c1 = box32(nb.b + 6, rf, E, lo);
+          if (c1 == B32_HIT && dLo > lo + 2 * E) { hr = true; er = lo; }
+          else orr = !(c1 == B32_MISS || dHi < lo - 2 * E);
+        } else {
+          ol = orr = true;
         }
-        if (__ballot(ol)) {  // unsettled lanes: the fp64 test
-          const ChildBox c = sload_child(nd, 0);
-          if (ol) hl = box_shadow_e<MASKOPS<F>>(c.mn, c.mx, ao, ad, ri, dist, el);
-        }
-        if (__ballot(orr)) {
-          const ChildBox c = sload_child(nd, 1);
-          if (orr) hr = box_shadow_e<MASKOPS<F>>(c.mn, c.mx, ao, ad, ri, dist, er);
-        }
-      } else {
-        const ChildBox c0 = sload_child(S.node + N, 0);
-        const ChildBox c1 = sload_child(S.node + N, 1);
-        cl.ref = c0.ref;
-        cr.ref = c1.ref;
-        if (in_mask_t<MASKOPS<F>>(act)) {
-          if (CNT) { ct.c[C_NODE]++; ct.c[C_BOX]++; }
-          hl = box_shadow_e<MASKOPS<F>>(c0.mn, c0.mx, ao, ad, ri, dist, el);
-          hr = box_shadow_e<MASKOPS<F>>(c1.mn, c1.mx, ao, ad, ri, dist, er);
-        }
+      }
+      if (__ballot(ol)) {  // unsettled lanes: the fp64 test
+        const ChildBox c = sload_child(nd, 0);
+        if (ol) hl = box_shadow_e<MASKOPS<F>>(c.mn, c.mx, ao, ad, ri, dist, el);
+      }
+      if (__ballot(orr)) {
+        const ChildBox c = sload_child(nd, 1);
+        if (orr) hr = box_shadow_e<MASKOPS<F>>(c.mn, c.mx, ao, ad, ri, dist, er);
       }
       const uint64_t R = __ballot(hr);
       const uint64_t H = __ballot(hl);
@@ -1690,13 +1445,8 @@ DEVI bool shadowed_(const SceneD& S, WRay& w, const Key& k, double dist, Counter
   }
   return false;
 }
-#ifdef RT_SHADOW_NOINLINE  // experiment: the shadow scan as a real call
-#define SHADOW_FN __device__ __attribute__((noinline))
-#else
-#define SHADOW_FN DEVI
-#endif
 template <bool CNT, uint32_t F, bool PK = false, bool WC = false>
-SHADOW_FN bool shadowed(const SceneD& S, WRay& w, const Key& k, double dist, Counters& ct, int li = 0) {
+DEVI bool shadowed(const SceneD& S, WRay& w, const Key& k, double dist, Counters& ct, int li = 0) {
   PROF_T0(t_all);
   const bool r = shadowed_<CNT, F, PK, WC>(S, w, k, dist, ct, li);
   PROF_ADD(t_all, R_SHADOW);
@@ -2094,112 +1844,13 @@ DEVI V diff_color(const SceneD& S, const MatD& m, const HitRec& h, const Key& k,
 // photon distance (per-axis differences, squares, same summation order) from bounds
 // no closer than any photon inside, and IEEE rounding is monotonic, so it never
 // exceeds the distance of a photon in the box: no qualifying photon is pruned.
-// The max-heap of (d^2, photon) lives in scratch (one 16-byte entry per slot); it is
-// filled by appending, heapified once when it first holds k entries, and afterwards
-// updated by replacing the root -- the same k-set as push-then-poll.
+// The k-set is found by selection (irradiance, below), not with a heap.
 static constexpr int KNN_MAX = 256;
-struct KnnE {
-  double d2;
-  int32_t i, pad;
-};
-DEVI void knn_sift_down(KnnE* h, int n, int j) {
-  const KnnE x = h[j];
-  while (true) {
-    int l = 2 * j + 1;
-    if (l >= n) break;
-    int m = l;
-    if (l + 1 < n && h[l + 1].d2 > h[l].d2) m = l + 1;
-    if (!(h[m].d2 > x.d2)) break;
-    h[j] = h[m];
-    j = m;
-  }
-  h[j] = x;
-}
 DEVI double box_d2(const double* mn, const double* mx, const double* p) {
   double d[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) d[c] = (p[c] < mn[c]) ? (p[c] - mn[c]) : ((p[c] > mx[c]) ? (p[c] - mx[c]) : 0.0);
   return d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
-}
-template <bool CNT>
-DEVI V irradiance_heap(const SceneD& S, V p, Counters& ct) {
-  if (S.nphoton == 0) return mk(0, 0, 0);
-  KnnE hp[KNN_MAX];
-  int hn = 0;
-  const int K = S.photonK < KNN_MAX ? S.photonK : KNN_MAX;
-  double maxd2 = S.photonMaxD2;
-  const double pos[3] = {p.x, p.y, p.z};
-  Stack st;  // (box d^2, node<<1 | side) ; the ray-traversal stack is idle during shading
-  int sp = 0;
-  int32_t N = S.photonRoot;
-  while (true) {
-    // N: a node to open
-    const NodeD& nd = S.pnode[N];
-    if (CNT) { ct.c[C_PHOTON]++; ct.c[C_WPHOTON]++; }
-    const double dl = box_d2(nd.lmin, nd.lmax, pos), dr = box_d2(nd.rmin, nd.rmax, pos);
-    const bool vl = dl < maxd2, vr = dr < maxd2;
-    // the nearer child now, the other one pushed (re-checked against the radius when popped)
-    int32_t next = -2;
-    if (vl || vr) {
-      const bool leftFirst = vl && (!vr || dl <= dr);
-      const int side = leftFirst ? 0 : 1;
-      if (vl && vr) { st.setT(sp, leftFirst ? dr : dl); st.setN(sp, (N << 1) | (1 - side)); sp++; }
-      next = (N << 1) | side;
-    }
-    while (true) {
-      if (next == -2) {  // pop
-        if (sp == 0) break;
-        --sp;
-        if (!(st.getT(sp) < maxd2)) continue;
-        next = st.getN(sp);
-      }
-      const NodeD& pn = S.pnode[next >> 1];
-      const int side = next & 1;
-      const int32_t child = side ? pn.right : pn.left;
-      if (child >= 0) { N = child; break; }
-      // leaf: scan its photons
-      const int start = side ? pn.pad[2] : pn.pad[0], count = side ? pn.padR[0] : pn.pad[1];
-      if (CNT) { ct.c[C_PHOTON] += count; ct.c[C_WPHOTON] += count; }
-      for (int q = 0; q < count; ++q) {
-        const double* ph = S.ppos + 3 * (size_t)(start + q);
-        const double dx = pos[0] - ph[0], dy = pos[1] - ph[1], dz = pos[2] - ph[2];
-        const double len2 = dx * dx + dy * dy + dz * dz;
-        if (len2 < maxd2) {
-          if (hn < K) {
-            hp[hn].d2 = len2; hp[hn].i = start + q;
-            hn++;
-            if (hn == K) {  // heapify once, then the radius is the k-th distance
-              for (int j = K / 2 - 1; j >= 0; --j) knn_sift_down(hp, K, j);
-              if (hp[0].d2 < maxd2) maxd2 = hp[0].d2;
-            }
-          } else {  // len2 < maxd2 = root: replace the farthest
-            hp[0].d2 = len2; hp[0].i = start + q;
-            knn_sift_down(hp, K, 0);
-            if (hp[0].d2 < maxd2) maxd2 = hp[0].d2;
-          }
-        }
-      }
-      next = -2;
-    }
-    if (next == -2 && sp == 0) {
-      // finished (the inner loop broke out at an empty stack)
-      break;
-    }
-  }
-  if (hn == 0) return mk(0, 0, 0);  // [null] -> 0 (Q20)
-  if (hn < K)
-    for (int j = hn / 2 - 1; j >= 0; --j) knn_sift_down(hp, hn, j);
-  const double rSq = hp[0].d2;
-  const double area = PI_F * rSq;
-  V res = mk(0, 0, 0);
-  while (hn > 0) {  // poll order: farthest first
-    const double* w = S.ppwr + 3 * (size_t)hp[0].i;
-    res.x += w[0]; res.y += w[1]; res.z += w[2];
-    hn--;
-    hp[0] = hp[hn];
-    knn_sift_down(hp, hn, 0);
-  }
-  return mk(res.x / area, res.y / area, res.z / area);
 }
 
 // Photon scan: f(d2, photon) for every photon with d2 < R2 (photon BVH, depth first,
@@ -2362,10 +2013,7 @@ DEVI void photon_scan_pk(const SceneD& S, const double* pos, double R2, Counters
 // neighbourhood (photon_scan, stacks in scratch: the pkT levels hold the counting histogram) instead of
 // one packet walking the union of all of them (those calls ran with ~6 lanes per wave step). Same
 // photons in the same order per lane: the image is unchanged. C5 (t11): frame 195.2 -> 196.2 ms, but
-// its slowest waves 47 -> 37 ms, the 8-GPU split's tail (profiles/r04f_*). RT_KNN_DIV = 0: packets only.
-#ifndef RT_KNN_DIV
-#define RT_KNN_DIV 1
-#endif
+// its slowest waves 47 -> 37 ms, the 8-GPU split's tail (profiles/r04f_*).
 #ifndef RT_KNN_DIV_FRAC
 #define RT_KNN_DIV_FRAC 2
 #endif
@@ -2374,16 +2022,15 @@ DEVI void photon_scan_pk(const SceneD& S, const double* pos, double R2, Counters
 #endif
 template <bool CNT, bool PWR = false, class Fn>
 DEVI void photon_scan_any(const SceneD& S, const double* pos, double R2, Counters& ct, Fn&& f, bool lanewise = false) {
-  if (PACKET && RT_KNN_DIV > 0 && lanewise) photon_scan<CNT, PWR, 0>(S, pos, R2, ct, f);
-  else if (PACKET) photon_scan_pk<CNT, PWR>(S, pos, R2, ct, f);
-  else photon_scan<CNT, PWR>(S, pos, R2, ct, f);
+  if (lanewise) photon_scan<CNT, PWR, 0>(S, pos, R2, ct, f);
+  else photon_scan_pk<CNT, PWR>(S, pos, R2, ct, f);
 }
 
 // The k nearest photons by selection instead of a heap (no per-lane memory): the
 // k-th smallest d^2 is bracketed by counting passes -- a histogram of equally spaced
-// buckets of the current window [lo, hi): 64 u16 buckets in LDS (knn_hist_pass; KNN_EDGES
-// = 16 u32 buckets when one lane has more than 65535 photons below hi, or 16 register
-// counters in builds without the packet kernels) -- until the window holding the k-th
+// buckets of the current window [lo, hi): 128 u8 buckets in LDS (knn_hist_pass; 64 u16 buckets
+// when a u8 bucket may have carried, KNN_EDGES = 16 u32 buckets when one lane has more than 65535
+// photons below hi) -- until the window holding the k-th
 // photon has <= KNN_SHELL photons; a last pass sums every photon below the window and
 // the nearest (k - below) window photons (kept sorted in registers). Same k-set and
 // largest d^2 as the heap; the powers are summed in scan order rather than the
@@ -2401,37 +2048,21 @@ DEVI void photon_scan_any(const SceneD& S, const double* pos, double R2, Counter
 // -- whose wide buckets then needed further passes. With that cheap recovery a tighter start window
 // pays: C5 193.4 -> 179.1 ms at START 1.15 (1.0 / 1.1 / 1.2 / 1.25 / 1.3: 251 / 180.4 / 180.5 / 183.0 /
 // 186.0 ms), the same k-sets and the same image bit for bit (profiles/r05j_*, r05k_*).
-#ifndef RT_KNN_EXTRAP
-#define RT_KNN_EXTRAP 1
-#endif
 #ifndef RT_KNN_START  // the start window: this many times the d^2 holding K photons at the node's density
 #define RT_KNN_START 1.15
 #endif
 #ifndef RT_KNN_EDGES
 #define RT_KNN_EDGES 16
 #endif
-#ifndef RT_KNN_LDS_HIST
-#define RT_KNN_LDS_HIST 1
-#endif
 static constexpr int KNN_SHELL = RT_KNN_SHELL;
-static constexpr int KNN_EDGES = RT_KNN_EDGES;  // counters per counting pass
-// counting passes through a per-lane LDS histogram (packet kernels: the traversal stack's
-// pkT levels are idle during shading) instead of KNN_EDGES register counters
-static constexpr bool KNN_LDS_HIST = PACKET && RT_KNN_LDS_HIST != 0;
-// KNN_H16: the LDS histogram as 64 u16 buckets (KNN_HB) instead of KNN_EDGES u32 ones
-#ifndef RT_KNN_H16
-#define RT_KNN_H16 1
-#endif
-static constexpr bool KNN_H16 = KNN_LDS_HIST && RT_KNN_H16 != 0;
-// KNN_H8: 128 u8 buckets in the same words, so a pass narrows the window 8x further than 16 u32
-// ones (a carry is detected by the buckets' sum; such a lane repeats the pass with the u16 buckets).
-// Passes per gather call drop, C5 179.9 -> 175.0 ms, same image (profiles/r05n_c5_knn_h8_ab.log).
-#ifndef RT_KNN_H8
-#define RT_KNN_H8 1
-#endif
-static constexpr bool KNN_H8 = KNN_H16 && RT_KNN_H8 != 0;
-static constexpr int KNN_HB = KNN_H8 ? 128 : KNN_H16 ? 64 : KNN_EDGES;
-static_assert(!KNN_LDS_HIST || KNN_SHELL * 64 * 12 <= PK_LDS * 64 * 8, "window list fits the pkT levels");
+static constexpr int KNN_EDGES = RT_KNN_EDGES;  // u32 buckets of the last-resort counting pass
+// The counting passes go through a per-lane LDS histogram (the traversal stack's pkT levels are idle
+// during shading): KNN_HB = 128 u8 buckets, four to a word, so a pass narrows the window 8x further
+// than 16 u32 ones (a carry is detected by the buckets' sum; such a lane repeats the pass with 64 u16
+// buckets, and with KNN_EDGES u32 ones past 65535 photons). Passes per gather call drop,
+// C5 179.9 -> 175.0 ms against the u16 first pass, same image (profiles/r05n_c5_knn_h8_ab.log).
+static constexpr int KNN_HB = 128;
+static_assert(KNN_SHELL * 64 * 12 <= PK_LDS * 64 * 8, "window list fits the pkT levels");
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
 // One counting pass over [lo, hi) through a per-lane LDS histogram (packet kernels: the
 // traversal stack's pkT levels are idle during shading) of NB equally spaced buckets:
@@ -2508,16 +2139,9 @@ DEVI void knn_hist_pass(const SceneD& S, const double* pos, double lo, double hi
 // LDS levels (idle once the counting selection's final pass is done); the lane runs alone.
 // PriorityQueue.offer adds before poll trims: the heap holds K + 1 entries for a moment (K <= KNN_MAX)
 static_assert((KNN_MAX + 1) * 12 + 64 * 4 <= PK_LDS * 64 * 8, "the replay's heap and frames fit the pkT levels");
-#ifndef RT_KNN_JAVA_CALL  // the replay as a real call: the hot variants' register allocation stays as it was
-#define RT_KNN_JAVA_CALL 1
-#endif
-#if RT_KNN_JAVA_CALL
-#define KNN_JAVA_FN __device__ __attribute__((noinline))
-#else
-#define KNN_JAVA_FN DEVI
-#endif
-KNN_JAVA_FN V knn_java_(const NodeD* pnode, const double* ppos, const double* ppwr, int32_t root, int K, double maxd2,
-                        double px, double py, double pz) {
+// the replay is a real call: the hot variants' register allocation stays as it was
+__device__ __attribute__((noinline)) V knn_java_(const NodeD* pnode, const double* ppos, const double* ppwr, int32_t root,
+                                                 int K, double maxd2, double px, double py, double pz) {
   const double pos[3] = {px, py, pz};
   const int32_t off = pnode[root].padR[2];
   if (off <= 0) return mk(0, 0, 0);  // no kd-tree (unreachable: every photon map carries one)
@@ -2602,9 +2226,6 @@ DEVI V knn_java(const SceneD& S, const double* pos) {
 
 template <bool CNT>
 DEVI V irradiance(const SceneD& S, V p, Counters& ct) {
-#ifdef RT_KNN_HEAP
-  return irradiance_heap<CNT>(S, p, ct);
-#endif
   if (S.nphoton == 0) return mk(0, 0, 0);
   const int K = S.photonK;
   const double R2max = S.photonMaxD2;
@@ -2645,16 +2266,16 @@ DEVI V irradiance(const SceneD& S, V p, Counters& ct) {
       N = nxt;
     }
   }
-  bool lw = false;  // RT_KNN_DIV experiment: scan lane by lane
-  if constexpr (PACKET && RT_KNN_DIV > 0) {
+  bool lw = false;  // scan lane by lane (photon_scan_any)
+  {
     const int f = (int)__builtin_ctzll(__ballot(1));
     const double fx = rdl(pos[0], f), fy = rdl(pos[1], f), fz = rdl(pos[2], f), r2 = rdl(R2dens, f);
     const double dx = pos[0] - fx, dy = pos[1] - fy, dz = pos[2] - fz;
-    // RT_KNN_DIV = 1: 1 / RT_KNN_DIV_FRAC of the lanes in this call (at least two) are farther than
-    // RT_KNN_DIV_R start radii; >= 2: at least that many lanes are
+    // 1 / RT_KNN_DIV_FRAC of the lanes in this call (at least two) are farther than RT_KNN_DIV_R
+    // start radii
     const int nfar = __popcll(__ballot(!(dx * dx + dy * dy + dz * dz <= (RT_KNN_DIV_R * RT_KNN_DIV_R) * r2)));
     const int nact = __popcll(__ballot(1));
-    lw = RT_KNN_DIV == 1 ? (nfar >= 2 && RT_KNN_DIV_FRAC * nfar >= nact) : nfar >= RT_KNN_DIV;
+    lw = nfar >= 2 && RT_KNN_DIV_FRAC * nfar >= nact;
   }
   // --- bracket the k-th d^2: window [lo, hi), `below` photons under lo
   PROF_CNT(R_KNN_NCALL);
@@ -2669,56 +2290,33 @@ DEVI V irradiance(const SceneD& S, V p, Counters& ct) {
     uint32_t total = 0, cPrev = 0, cAt = 0;
     int kb = -1;
     int ne = NE;  // this lane's edges in this pass: e[k] = lo + (k + 1) w, w = (hi - lo) / ne
-    if constexpr (KNN_LDS_HIST) {
-      bool ovf = false;
-      knn_hist_pass<CNT, KNN_HB, KNN_H16 && !KNN_H8, KNN_H8>(S, pos, lo, hi, K, ct, total, kb, cPrev, cAt, ovf, lw);
-      ne = KNN_HB;
-      if (KNN_H8 && __ballot(ovf)) {  // a u8 bucket may have carried: this pass again with u16 buckets
-        if (ovf) {
-          total = cPrev = cAt = 0; kb = -1; ovf = false;
-          knn_hist_pass<CNT, 64, true>(S, pos, lo, hi, K, ct, total, kb, cPrev, cAt, ovf, lw);
-          ne = 64;
-        }
+    bool ovf = false;
+    knn_hist_pass<CNT, KNN_HB, false, true>(S, pos, lo, hi, K, ct, total, kb, cPrev, cAt, ovf, lw);
+    ne = KNN_HB;
+    if (__ballot(ovf)) {  // a u8 bucket may have carried: this pass again with u16 buckets
+      if (ovf) {
+        total = cPrev = cAt = 0; kb = -1; ovf = false;
+        knn_hist_pass<CNT, 64, true>(S, pos, lo, hi, K, ct, total, kb, cPrev, cAt, ovf, lw);
+        ne = 64;
       }
-      if (KNN_H16 && __ballot(ovf)) {  // > 65535 photons below hi: this pass again with u32 buckets
-        if (ovf) {
-          total = cPrev = cAt = 0; kb = -1;
-          knn_hist_pass<CNT, NE, false>(S, pos, lo, hi, K, ct, total, kb, cPrev, cAt, ovf, lw);
-          ne = NE;
-        }
+    }
+    if (__ballot(ovf)) {  // > 65535 photons below hi: this pass again with u32 buckets
+      if (ovf) {
+        total = cPrev = cAt = 0; kb = -1;
+        knn_hist_pass<CNT, NE, false>(S, pos, lo, hi, K, ct, total, kb, cPrev, cAt, ovf, lw);
+        ne = NE;
       }
-    } else {
-      const double w = (hi - lo) * (1.0 / NE);
-      double e[NE];
-#pragma unroll
-      for (int k = 0; k < NE - 1; ++k) e[k] = lo + (k + 1) * w;
-      e[NE - 1] = hi;
-      uint32_t c[NE];
-#pragma unroll
-      for (int k = 0; k < NE; ++k) c[k] = 0;
-      photon_scan_any<CNT>(S, pos, hi, ct, [&](double d2, int, V) {
-#pragma unroll
-        for (int k = 0; k < NE; ++k) c[k] += (d2 < e[k]) ? 1u : 0u;
-      });
-      total = c[NE - 1];
-#pragma unroll
-      for (int k = 0; k < NE; ++k)  // selects, no dynamic register indexing
-        if (kb < 0 && (int)c[k] >= K) { kb = k; cAt = c[k]; cPrev = k ? c[k - 1] : 0; }
     }
     PROF_ADD(t_kc, R_KNN_COUNT);
     PROF_CNT(R_KNN_NPASS);
     if ((int)total < K) {  // only possible for the start window: widen it
       if (hi == R2max) { all = true; break; }
-#if RT_KNN_EXTRAP
       // every photon under hi is in the set: the window moves above it, and grows by the
       // surface-density extrapolation (count ~ d^2) of what is still missing, at most to R2far
       const double ext = total > 0 ? hi * (RT_KNN_START * K / (double)total) : R2far;
       lo = hi;
       below = (int)total;
       hi = (hi < R2far) ? fmin(R2far, ext) : R2max;
-#else
-      hi = (hi < R2far) ? R2far : R2max;
-#endif
       continue;
     }
     // the window becomes [e[kb - 1], e[kb]) with e[k] = lo + (k + 1) w, e[ne - 1] = hi (the
@@ -2751,38 +2349,25 @@ DEVI V irradiance(const SceneD& S, V p, Counters& ct) {
       }
     }
   };
-  if constexpr (KNN_LDS_HIST) {
-    // window photons are appended to a per-lane list in LDS during the scan and sorted once
-    // after it by the same insertion, in the same (scan) order. The window holds <= KNN_SHELL
-    // photons unless the bracket ran out of levels, which only a window of equal distances
-    // does: the list then keeps the first KNN_SHELL, as the sorted shell would.
-    lds_f64* ld = pkT() + __lane_id();
-    lds_i32* li = (lds_i32*)(pkT() + KNN_SHELL * 64) + __lane_id();
-    photon_scan_any<CNT, true>(S, pos, all ? R2max : hi, ct, [&](double d2, int i, V w) {
-      if (all || d2 < lo) {
-        res.x += w.x; res.y += w.y; res.z += w.z;
-        if (d2 > rSq) rSq = d2;
-        n++;
-      } else {
-        if (m < KNN_SHELL) { ld[m * 64] = d2; li[m * 64] = i; }
-        m++;
-      }
-    }, lw);
+  // window photons are appended to a per-lane list in LDS during the scan and sorted once
+  // after it by the same insertion, in the same (scan) order. The window holds <= KNN_SHELL
+  // photons unless the bracket ran out of levels, which only a window of equal distances
+  // does: the list then keeps the first KNN_SHELL, as the sorted shell would.
+  lds_f64* ld = pkT() + __lane_id();
+  lds_i32* li = (lds_i32*)(pkT() + KNN_SHELL * 64) + __lane_id();
+  photon_scan_any<CNT, true>(S, pos, all ? R2max : hi, ct, [&](double d2, int i, V w) {
+    if (all || d2 < lo) {
+      res.x += w.x; res.y += w.y; res.z += w.z;
+      if (d2 > rSq) rSq = d2;
+      n++;
+    } else {
+      if (m < KNN_SHELL) { ld[m * 64] = d2; li[m * 64] = i; }
+      m++;
+    }
+  }, lw);
 #pragma unroll
-    for (int k = 0; k < KNN_SHELL; ++k)
-      if (k < m) shell_insert(ld[k * 64], li[k * 64]);
-  } else {
-    photon_scan_any<CNT, true>(S, pos, all ? R2max : hi, ct, [&](double d2, int i, V w) {
-      if (all || d2 < lo) {
-        res.x += w.x; res.y += w.y; res.z += w.z;
-        if (d2 > rSq) rSq = d2;
-        n++;
-      } else {
-        shell_insert(d2, i);
-        m++;
-      }
-    });
-  }
+  for (int k = 0; k < KNN_SHELL; ++k)
+    if (k < m) shell_insert(ld[k * 64], li[k * 64]);
   // a tie across the k-th position: window photons `need` and `need + 1` (1-based) at the same
   // distance. Which of them the reference keeps is its kd-tree order and heap layout: such a lane
   // replays find_near.
@@ -2862,7 +2447,7 @@ DEVI V rot_axis(V v1, V u, double thet) {  // rotVecAroundAxis (DistRayTracer.ja
             (uxyC1 + uzS) * v1.x + (uy2 * oneMC + cT) * v1.y + (uyzC1 - uxS) * v1.z,
             (uxzC1 - uyS) * v1.x + (uyzC1 + uxS) * v1.y + (uz2 * oneMC + cT) * v1.z);
 }
-// U: L is wave-uniform (light_sum's loop): its fields as scalar loads
+// U: L is wave-uniform (the compacted shadow rays' shadow_ray): its fields as scalar loads
 template <bool U = false>
 DEVI V disk_pos(const LightD& L, const Key& k, uint32_t kk) {  // getRandomDiskPos (myLight.java:251-258)
   const int32_t li = pld<U>(&L.index);
@@ -2914,7 +2499,7 @@ DEVI V light_sum(const SceneD& S, const MatD& m, const HitRec& h, V tex, const K
     const V lorg = mk(sload(L.origin), sload(L.origin + 1), sload(L.origin + 2));
     const V lcol = mk(sload(L.color), sload(L.color + 1), sload(L.color + 2));
     const bool disk = (F & FT_LIGHTX) && ltype == 2;
-    V lo = disk ? disk_pos<(RT_ULOAD & 2) != 0>(L, k, 0) : lorg;
+    V lo = disk ? disk_pos(L, k, 0) : lorg;
     V ln = xpt(lg, lo);
     double lm;
     ln = nrmz_m(mk(ln.x - h.fwd.x, ln.y - h.fwd.y, ln.z - h.fwd.z), lm);
@@ -2929,17 +2514,16 @@ DEVI V light_sum(const SceneD& S, const MatD& m, const HitRec& h, V tex, const K
     if (KN_DIST<F> && sload(&L.pad[0]) == 1) {
       t = lm;  // the light sits at lorg in world space: |fwd - lorg| is the magnitude just divided by
     } else {
-      V lo2 = disk ? disk_pos<(RT_ULOAD & 2) != 0>(L, k, 2) : lorg;
+      V lo2 = disk ? disk_pos(L, k, 2) : lorg;
       t = sqrt((((sr.o.x - lo2.x) * (sr.o.x - lo2.x)) + ((sr.o.y - lo2.y) * (sr.o.y - lo2.y))) + ((sr.o.z - lo2.z) * (sr.o.z - lo2.z)));
     }
     double ltMult = 1;
     if (CNT) ct.c[C_LIGHT]++;
     WCNT(C_WLIGHT, 1);  // the light record: scalar loads, once per wave
     if ((F & FT_LIGHTX) && ltype == 1) {  // mySpotLight.intersectCheck / calcT_Mult (myLight.java:77-82,159-163)
-      constexpr bool U = (RT_ULOAD & 2) != 0;
-      double angle = jf::acos(-1 * dot(sr.d, pld3<U>(L.orient)));
-      const double inR = pld<U>(&L.innerRad), outR = pld<U>(&L.outerRad);
-      ltMult = (angle < inR) ? 1 : (angle > outR) ? 0 : (outR - angle) / pld<U>(&L.radDiff);
+      double angle = jf::acos(-1 * dot(sr.d, ld3(L.orient)));
+      const double inR = L.innerRad, outR = L.outerRad;
+      ltMult = (angle < inR) ? 1 : (angle > outR) ? 0 : (outR - angle) / L.radDiff;
     }
     if (ltMult == 0) continue;
     if (CNT) ct.c[C_SHADOW]++;
@@ -2950,7 +2534,7 @@ DEVI V light_sum(const SceneD& S, const MatD& m, const HitRec& h, V tex, const K
 #ifdef RT_PROF_NOSHADOW  // profiling builds only (tools/variant_sweep.py): results differ
     if (false)
 #endif
-    if (shadowed<CNT, F, PACKET, WAVE_CULL<F>>(S, sr, sk, t, ct, li)) continue;
+    if (shadowed<CNT, F, true, WAVE_CULL<F>>(S, sr, sk, t, ct, li)) continue;
     renorm<KN_UNIT<F>>(sr);  // shadowRay.direction._normalize()
     if (STASH) {
       if (F & FT_LIGHTX) ltMult = unstash(SL_LTM);
@@ -3072,14 +2656,12 @@ DEVI void kt_of(const SceneD& S, int32_t ktm, double ik[2]) {
 // two scalars instead of two colours; the B child's medium is the material again.
 // Only the fields a node's case needs are written (the frame stack lives in scratch).
 enum : uint8_t { FM_REFL = 0, FM_FRESNEL = 1, FM_SIMPLE = 2 };  // weight rule of a frame
-// FRAME_SLIM (trace_sample's frames): the rule is rebuilt from the material, omtr from tr (trans_split
-// forms omtr as 1 - tr on every path), the node id from the returning child's id and the generation
-// from the stack index, so a Fresnel frame writes 24 B fewer to scratch. C4: writes 143.9 -> 127.0 GB
-// per frame, 456.9 -> 453.8 ms; C5 174.3 -> 173.9 ms; same images (profiles/r05q_frame_slim_ab.log)
-#ifndef RT_FRAME_SLIM
-#define RT_FRAME_SLIM 1
-#endif
-static constexpr bool FRAME_SLIM = RT_FRAME_SLIM != 0;
+// Slim frames (trace_sample's; shade_node<SLIM = true>): the rule is rebuilt from the material, omtr
+// from tr (trans_split forms omtr as 1 - tr on every path), the node id from the returning child's id
+// and the generation from the stack index, so a Fresnel frame writes 24 B fewer to scratch (mode, wa,
+// node and gen are left unwritten). C4: writes 143.9 -> 127.0 GB per frame, 456.9 -> 453.8 ms;
+// C5 174.3 -> 173.9 ms; same images (profiles/r05q_frame_slim_ab.log). The level-synchronous
+// kernels (wavefront.h) write every field.
 template <uint32_t F>
 struct FrameT {
   V local, acc, org, dB;  // acc: child A's weighted colour, kept only while B is traced
@@ -3102,7 +2684,7 @@ using FrameOf = typename std::conditional<(F & FT_TRANS) != 0, FrameT<F>, FrameR
 // children. Returns the number of children (0..2); child A is written to `a`, the local colour to
 // `loc` -- not to the frame: the caller stores it there only when the node pushes one (a node
 // without children keeps it in registers; the frame stack lives in scratch).
-template <bool CNT, uint32_t F, bool SLIM = FRAME_SLIM>  // SLIM: the frame's derivable fields are not written
+template <bool CNT, uint32_t F, bool SLIM = true>  // SLIM: the frame's derivable fields are not written
 DEVI int shade_node(const SceneD& S, const HitRec& h, const Child& in, const Key& k, FrameOf<F>& Fr, V& loc,
                     Child& a, bool& branch, Counters& ct) {
   const MatD& m = S.mat[h.mat];
@@ -3223,27 +2805,17 @@ static constexpr int MAX_FRAMES = 7;  // gen < numRays-2 = 6 -> at most 6 nodes 
 // (C3: ~30 B of scratch writes per sample). It waits in the lane's own LDS stash slots instead:
 // every LDS slot the other lanes write while tracing and shading is their own ([slot][lane]:
 // traversal levels, stash slots), except the per-lane stacks of the photon scans and of the
-// lane-wise BVH experiment (RT_LANE_DIV), which index [level][lane] ints over the same bytes -- so
-// not in photon variants nor with RT_LANE_DIV. Measured (profiles/r04z_res_lds_ab.txt): C3 writes
+// traversals of lane-by-lane ray queries, which index [level][lane] ints over the same bytes -- so
+// not in photon variants. Measured (profiles/r04z_res_lds_ab.txt): C3 writes
 // 1.36 -> 1.31 GB per frame at the same time; C4's transparent variant lost 1.8 % then (its allocation
 // shifted) and gains since round 5 (below).
 // Round 5, after the scalar primitive loads and slim frames shifted C4's allocation: the per-pixel
 // sums and the finished colour in LDS pay in the transparent variants without a photon map too --
 // C4 455.3 -> 447.4 ms, writes 127.0 -> 113.1 GB per frame; C5's photon variant keeps its sums in
 // VGPRs (177.6 vs 174.4 ms with them in LDS), same images (profiles/r05z_trans_lds_ab.log)
-#ifndef RT_RES_LDS_TRANS
-#define RT_RES_LDS_TRANS 1
-#endif
-#ifndef RT_SUMS_LDS_TRANS
-#define RT_SUMS_LDS_TRANS 1
-#endif
-#ifndef RT_RES_LDS
-#define RT_RES_LDS 1
-#endif
 enum { SL_RES = SL_RGB };
 template <uint32_t F>
-static constexpr bool RES_LDS = RT_RES_LDS != 0 && STASH_SHADE && (F & FT_PHOTON) == 0 &&
-                                ((F & FT_TRANS) == 0 || RT_RES_LDS_TRANS != 0) && RT_LANE_DIV == 0;
+static constexpr bool RES_LDS = STASH_SHADE && (F & FT_PHOTON) == 0;
 
 // reflectRay (myScene.java:907-914) for the whole shading tree of one camera sample
 template <bool CNT, uint32_t F>
@@ -3265,7 +2837,7 @@ DEVI V trace_sample(const SceneD& S, V org, V dir, Key k, Counters& ct) {
       Best b = miss();
 #else
       PKSTAT(P_RAY_STEP, __ballot(1));
-      Best b = closest<CNT, F, PACKET>(S, w, k, ct);
+      Best b = closest<CNT, F, true>(S, w, k, ct);
 #endif
       if (b.t == DMAX) {
         PROF_T0(t_bg);
@@ -3304,7 +2876,7 @@ DEVI V trace_sample(const SceneD& S, V org, V dir, Key k, Counters& ct) {
     }
     // deliver finished colours upward
     bool spawned = false;
-    uint32_t cn = in.node;  // FRAME_SLIM: the node id of the subtree that just finished
+    uint32_t cn = in.node;  // the node id of the subtree that just finished
     while (sp > 0) {
       FrameOf<F>& P = fr[sp - 1];
       if constexpr ((F & FT_TRANS) == 0) {  // the only child has returned
@@ -3316,18 +2888,12 @@ DEVI V trace_sample(const SceneD& S, V org, V dir, Key k, Counters& ct) {
         // the weights of the reference's frame, rebuilt from the material (same products)
         const MatD& m = S.mat[P.mat];
         const uint8_t ph = P.phase;
-        uint8_t mode;
-        double wa;
-        if (FRAME_SLIM) {  // the frame's rule from its material (shade_node's case split), omtr = 1 - tr
-          const bool strans = m.simple && (m.ktrans > 0);
-          const bool trans = !m.simple && ((m.ktrans > 0) || (m.perm > 0.0));
-          mode = (trans || strans) ? (strans ? FM_SIMPLE : FM_FRESNEL) : FM_REFL;
-          wa = 1 - P.wb;
-        } else {
-          mode = P.mode;
-          wa = P.wa;
-        }
-        const uint32_t pn = cn >> 1;  // FRAME_SLIM: this frame's node id (its child's id / 2)
+        // the frame's rule from its material (shade_node's case split), omtr = 1 - tr
+        const bool strans = m.simple && (m.ktrans > 0);
+        const bool trans = !m.simple && ((m.ktrans > 0) || (m.perm > 0.0));
+        const uint8_t mode = (trans || strans) ? (strans ? FM_SIMPLE : FM_FRESNEL) : FM_REFL;
+        const double wa = 1 - P.wb;
+        const uint32_t pn = cn >> 1;  // this frame's node id (its child's id / 2)
         cn = pn;
         V acc;
         if (ph == 1) {
@@ -3340,8 +2906,7 @@ DEVI V trace_sample(const SceneD& S, V org, V dir, Key k, Counters& ct) {
             P.phase = 2;
             P.acc = acc;
             in.o = P.org; in.d = P.dB;
-            if (FRAME_SLIM) { in.gen = sp; in.node = pn * 2 + 1; }  // a frame's stack index is its node's generation
-            else { in.gen = P.gen + 1; in.node = P.node * 2 + 1; }
+            in.gen = sp; in.node = pn * 2 + 1;  // a frame's stack index is its node's generation
             in.ktm = (mode == FM_SIMPLE) ? -1 : P.mat;
             if (STASH_SHADE) { stash3(SL_RAYO, in.o); stash3(SL_RAYD, in.d); }
             if (CNT) ct.c[C_REFL]++;
@@ -3502,7 +3067,7 @@ DEVI V light_sum_w(const SceneD& S, bool hit, int32_t mat, const Key& k, Counter
 #ifdef RT_PROF_NOSHADOW  // profiling builds only (tools/variant_sweep.py): results differ
           if (true) {
 #else
-          if (!shadowed<CNT, F, PACKET>(S, sr, sk, sh.dist, ct)) {
+          if (!shadowed<CNT, F, true>(S, sr, sk, sh.dist, ct)) {
 #endif
             renorm<KN_UNIT<F>>(sr);  // shadowRay.direction._normalize()
             res = (int)sr.ver;
@@ -3692,7 +3257,7 @@ DEVI V trace_sample_w(const SceneD& S, V org, V dir, Key k, bool live, Counters&
       w.o = in.o; w.d = nrmz(in.d); w.d0 = w.d; w.stable = false; w.moved = false; w.ver = 0;  // myRay ctor
       k.node = in.node;
       PKSTAT(P_RAY_STEP, __ballot(1));
-      const Best bh = closest<CNT, F, PACKET>(S, w, k, ct);
+      const Best bh = closest<CNT, F, true>(S, w, k, ct);
       if (bh.t == DMAX) {
         PROF_T0(t_bg);
         c = background<CNT, F>(S, w, ct);
@@ -3771,27 +3336,6 @@ DEVI V trace_sample_w(const SceneD& S, V org, V dir, Key k, bool live, Counters&
   return out;
 }
 
-// XCD-aware tile order. Workgroups are dealt round-robin to the 8 XCDs (block b -> XCD
-// b % 8), each with its own L2. With XCD_CHUNKS = k > 0 the row-major tile list is cut
-// into 8k contiguous chunks and XCD x renders chunks x, x+8, ...: each L2 then sees a
-// few image bands (and the part of the scene they show) instead of the whole frame.
-#ifndef RT_XCD_CHUNKS
-#define RT_XCD_CHUNKS 0
-#endif
-static constexpr int XCD_CHUNKS = RT_XCD_CHUNKS;
-__host__ __device__ inline int xcd_grid(int ntiles) {
-  if constexpr (XCD_CHUNKS == 0) return ntiles;
-  const int nch = 8 * (XCD_CHUNKS ? XCD_CHUNKS : 1), csz = (ntiles + nch - 1) / nch;
-  return nch * csz;
-}
-DEVI int tile_of_block(int b, int ntiles) {
-  if constexpr (XCD_CHUNKS == 0) return b;
-  const int nch = 8 * (XCD_CHUNKS ? XCD_CHUNKS : 1), csz = (ntiles + nch - 1) / nch;
-  const int xcd = b & 7, slot = b >> 3;
-  const int t = ((slot / csz) * 8 + xcd) * csz + slot % csz;
-  return t < ntiles ? t : -1;
-}
-
 #ifndef RT_RENDER_WAVES
 #define RT_RENDER_WAVES 4
 #endif
@@ -3799,13 +3343,9 @@ DEVI int tile_of_block(int b, int ntiles) {
 // pixel geometry by shifts, the per-pixel sum on three channel lanes, the average of 2^k samples as a
 // product. On in the variants without transparency, extra cameras, lens or column step (F = 0 and
 // FT_PRIM; C3's gain is in DESIGN.md §6). C4's and C5's variants ran 0.7-1.4 % slower with it through
-// their register allocation, so they, and every other variant, compile the code they had
-// (RT_WAVE_FAST=0: every variant does).
-#ifndef RT_WAVE_FAST
-#define RT_WAVE_FAST 1
-#endif
+// their register allocation, so they, and every other variant, compile the code they had.
 template <uint32_t F>
-constexpr bool wave_fast() { return RT_WAVE_FAST != 0 && (F & (FT_TRANS | FT_CAMX | FT_DOF | FT_PASS)) == 0; }
+constexpr bool wave_fast() { return (F & (FT_TRANS | FT_CAMX | FT_DOF | FT_PASS)) == 0; }
 // where a lane's pixel is: sample lane j of pixel pl of the wave's tile
 struct PixGeo {
   int j, pl, ci, col, ri, row;
@@ -3905,8 +3445,10 @@ render_kernel(SceneD S, ParamsD P, float* __restrict__ rgb, int32_t* __restrict_
   const int ncols = (F & FT_PASS) ? (P.W + P.colStep - 1) / P.colStep : P.W;
   constexpr bool FAST = wave_fast<F>();
   const int tilesX = FAST ? (ncols + P.tw - 1) >> __builtin_ctz((unsigned)P.tw) : (ncols + P.tw - 1) / P.tw;  // tw: a power of two
-  int tile = tile_of_block(blockIdx.x, tilesX * ((P.nrows + P.th - 1) / P.th));
-  if (tile < 0) return;  // padding block of the XCD mapping (whole workgroup)
+  int tile = blockIdx.x;  // one workgroup per tile, dealt to the XCDs in launch order (or P.order's)
+  // Never taken (a grid has fewer than 2^31 blocks), but the compiler does not assume so, and without
+  // the early exit it allocates every variant's registers differently from the kernels as measured.
+  if (tile < 0) return;
   if (P.order) tile = P.order[tile];
   const unsigned long long tl0 = __builtin_amdgcn_s_memrealtime();  // wave start (tcost / timeline)
   PROF_T0(tk0);
@@ -3939,9 +3481,10 @@ render_kernel(SceneD S, ParamsD P, float* __restrict__ rgb, int32_t* __restrict_
   // per-pixel sums. SUMS_LDS variants keep them in LDS across the shading trees -- G >= 2 in
   // sums[] (sample order), G == 1 (spp = 1, one round) as the lane's colour in cbuf; the others
   // in registers (rs / gs / bs; the 1-spp non-DOF path keeps its one colour there). Which is
-  // faster depends on the variant's register allocation (measured: C3's F = 0 gains, C4's
-  // transparent variant loses 6 %).
-  constexpr bool SUMS_LDS = (F & FT_TRANS) == 0 || (RT_SUMS_LDS_TRANS != 0 && (F & FT_PHOTON) == 0);
+  // faster depends on the variant's register allocation (measured: C3's F = 0 gains; C4's
+  // transparent variant lost 6 % at first and gains since the slim frames, trace_sample's RES_LDS
+  // comment; C5's photon variant keeps them in registers).
+  constexpr bool SUMS_LDS = (F & FT_TRANS) == 0 || (F & FT_PHOTON) == 0;
   double rs = 0, gs = 0, bs = 0;
   lds_f64* sums = (lds_f64*)((lds_u8*)rt_lds + LDS_BYTES);
   if (SUMS_LDS && G > 1 && (lane & (G - 1)) == 0) {

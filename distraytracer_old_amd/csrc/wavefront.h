@@ -118,7 +118,7 @@ DEVI WfOut wf_shade(const SceneD& S, const Child& in, Key& k, WfNode& rec) {
   WRay w;
   w.o = in.o; w.d = nrmz(in.d); w.d0 = w.d; w.stable = false; w.moved = false; w.ver = 0;  // myRay ctor
   k.node = in.node;
-  Best b = closest<false, F, PACKET>(S, w, k, ct);
+  Best b = closest<false, F, true>(S, w, k, ct);
   rec.kind = 0;
   if (b.t == DMAX) {
     r.c = background<false, F>(S, w, ct);

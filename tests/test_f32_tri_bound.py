@@ -1,4 +1,4 @@
-"""The fp32 triangle edge pre-test (csrc/trace_kernels.h tri_f32_out, RT_F32_TRI) never rejects a lane
+"""The fp32 triangle edge pre-test (csrc/trace_kernels.h tri_f32_out) never rejects a lane
 that the fp64 triangle test accepts (CPU, numpy).
 
 The pre-test may only say "this lane's triangle test returns false"; the GPU parity tests cover the

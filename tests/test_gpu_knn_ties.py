@@ -149,7 +149,7 @@ def test_gather_ties_at_the_largest_k(tmp_path, seed):
 
 
 def test_gather_u8_bucket_carry_falls_back(tmp_path):
-    """The counting passes keep 128 u8 buckets per lane (KNN_H8); a bucket holding more than 255
+    """The counting passes keep 128 u8 buckets per lane (KNN_HB); a bucket holding more than 255
     photons carries into its neighbour, which the pass detects from the buckets' sum and repeats with
     u16 buckets. 300 photons at distinct distances within 3e-7 of radius 1 around the query points
     land in one bucket of the first pass: the k = 100 nearest must still be the oracle's."""

@@ -5,7 +5,10 @@
   python tools/variant_sweep.py build            # -> tools/_variants/*.so
   python tools/variant_sweep.py run [--cfg C3]   # on the GPU: ms/frame + ARGB hash per build
 
-Every build must give the same ARGB hash (the specialisations change speed, not results).
+Every build must give the same ARGB hash (the specialisations change speed, not results), the
+profiling builds (RT_PROF_*) excepted. Every define below names a macro that csrc/ reads
+(tests/test_variant_table.py); switches whose A/B is settled are folded into the code and listed in
+DESIGN.md "Retired switches".
 """
 from __future__ import annotations
 
@@ -24,7 +27,6 @@ VARIANTS = {  # name -> -D defines; names like "s12w4" are parsed (see defines_o
     "nosec": ["RT_PROF_NOSECONDARY"],
     "primary": ["RT_PROF_NOSHADOW", "RT_PROF_NOSECONDARY"],
     "nogather": ["RT_PROF_NOGATHER"],
-    "knnheap": ["RT_KNN_HEAP"],
     "nophong": ["RT_PROF_NOPHONG"],
     "notex": ["RT_PROF_NOTEX"],                # object textures -> plain diffuse
     "noshade": ["RT_PROF_NOSHADE"],            # camera rays traced, no hit record / shading
@@ -42,129 +44,34 @@ VARIANTS = {  # name -> -D defines; names like "s12w4" are parsed (see defines_o
     "minreg": ["-Xarch_device", "-mllvm=--amdgpu-sched-strategy=iterative-minreg"],
     "trkminreg": ["-Xarch_device", "-mllvm=--amdgpu-use-amdgpu-trackers=1", "-Xarch_device",
                   "-mllvm=--amdgpu-sched-strategy=iterative-minreg"],
-    "ed8": [],
-    "ed16": ["RT_KNN_EDGES=16"],
-    "ed32": ["RT_KNN_EDGES=32"],
-    "ed16sh12": ["RT_KNN_EDGES=16", "RT_KNN_SHELL=12"],
-    "hist0": ["RT_KNN_LDS_HIST=0"],            # kNN counting in registers (results equal)
+    # photon gather: sizes and thresholds (defaults: EDGES 16, SHELL 10, START 1.15, DIV_FRAC 2, DIV_R 2.0,
+    # PH_BATCH 1, PH_VLOAD 1)
+    "ed32": ["RT_KNN_EDGES=32"],               # u32 buckets of the last-resort counting pass
+    "sh12": ["RT_KNN_SHELL=12"],               # window list in LDS: up to 12 photons
     "h32b2": ["RT_KNN_EDGES=32", "RT_PH_BATCH=2"],
     "h32sh12": ["RT_KNN_EDGES=32", "RT_KNN_SHELL=12"],
-    "sh10": ["RT_KNN_SHELL=10"],               # window list in LDS: up to 10 photons
-    "h32": ["RT_KNN_EDGES=32"],
-    "h32sh10": ["RT_KNN_EDGES=32", "RT_KNN_SHELL=10"],
-    "h64": ["RT_KNN_H16=1"],                   # 64 u16 LDS buckets per counting pass
-    "h64s10": ["RT_KNN_H16=1", "RT_KNN_SHELL=10"],
-    "vl": ["RT_PH_VLOAD=1"],                   # leaf photons: vector load + v_readlane
-    "vl2": ["RT_PH_VLOAD=2"],                  # ... two independent distances per step
+    "vl2": ["RT_PH_VLOAD=2"],                  # leaf photons (vector load + v_readlane): two independent distances per step
     "vl4": ["RT_PH_VLOAD=4"],
-    "h64s10reg": ["RT_KNN_H16=1", "RT_KNN_SHELL=10", "RT_PROF_REGIONS"],
+    "st10": ["RT_KNN_START=1.0"],              # the start window: x the d^2 holding K photons at the node's density
+    "st11": ["RT_KNN_START=1.1"],
+    "st12": ["RT_KNN_START=1.2"],
+    "st125": ["RT_KNN_START=1.25"],
+    "st13": ["RT_KNN_START=1.3"],
+    "kdf4": ["RT_KNN_DIV_FRAC=4"],             # lane-by-lane scans when 1/4 (1/1) of a call's lanes are far apart
+    "kdf1": ["RT_KNN_DIV_FRAC=1"],
+    "kdr4": ["RT_KNN_DIV_R=4.0"],              # ... farther than 4 (1) start radii from the first lane's point
+    "kdr1": ["RT_KNN_DIV_R=1.0"],
     "tl": ["RT_PROF_TIMELINE"],               # workgroup timeline (tools/timeline.py)
     "pkstat": ["RT_PROF_PKSTAT"],             # packet lane utilisation (tools/pkstat.py)
     "shnoquad": ["RT_PROF_SH_NOQUAD"],         # shadow scan without quads / planes
     "shnoimpl": ["RT_PROF_SH_NOIMPL"],         # shadow scan without implicit primitives
     "shnoaccel": ["RT_PROF_SH_NOACCEL"],       # shadow scan without BVHs / lists
-    "shinline": ["RT_SHADOW_NOINLINE"],        # shadow scan as a real call (results equal)
     "shscan": ["RT_PROF_SH_SCANONLY"],         # shadow rays: the top-level scan only, no tests
-    "shnoacc": ["RT_PROF_SH_NOACCEL"],         # shadow rays: no BVH / list entries
     "regions": ["RT_PROF_REGIONS"],           # wave time per region (tools/regions.py)
-    "nf0": ["RT_NEAREST_FIRST=0"],             # closest hit in the reference order only (round 2)
-    "nf1": [],                                 # nearest-first closest hit where it applies (default)
-    "nopio": ["RT_JF_NPIO2=0"],                # rem_pio2 without e_rem_pio2.c's npio2_hw shortcut
-    "an0": ["RT_ANY_NEAR=0"],
-    "wc0": ["RT_WAVE_CULL=0"],                 # no wave-level shadow candidates (the r03l kernel)
-    "wc1": [],                                 # wave-level shadow candidates per shading step (default)
     "base": [],                                # the default build
-    "wp1": [],                                 # the default build (+ quad / plane sides in the wave cull)
-    "wtri": ["RT_WC_TRI=1"],                   # the wave cull in the triangles-only variant (C3) too
-    "nft": ["RT_NF_TRANS=1"],                  # nearest-first closest hit in C4's transparent variant
-    "ant": ["RT_AN_TRANS=1"],                  # nearest-first any-hit order there
-    "nftant": ["RT_NF_TRANS=1", "RT_AN_TRANS=1"],
-    "nfan0": ["RT_NEAREST_FIRST=0", "RT_ANY_NEAR=0"],
-    "ld8": ["RT_LANE_DIV=8"],                  # divergent waves: per-lane BVH traversal (closest hit)
-    "ld16": ["RT_LANE_DIV=16"],
-    "ld32": ["RT_LANE_DIV=32"],
-    "ld16c99": ["RT_LANE_DIV=16", "RT_LANE_DIV_COS=0.99"],
-    "kd1": ["RT_KNN_DIV=1"],                   # ... when half of the call's lanes are far apart
-    "ld1": ["RT_LANE_DIV=1"],
-    "nfcode": ["RT_NF_CODE=1"],
-    "kd1f4": ["RT_KNN_DIV=1", "RT_KNN_DIV_FRAC=4"],
-    "kd1f1": ["RT_KNN_DIV=1", "RT_KNN_DIV_FRAC=1"],
-    "kd1r4": ["RT_KNN_DIV=1", "RT_KNN_DIV_R=4.0"],
-    "kd1r1": ["RT_KNN_DIV=1", "RT_KNN_DIV_R=1.0"],
-    "kd8": ["RT_KNN_DIV=8"],                   # divergent query points: per-lane photon scans
-    "kd16": ["RT_KNN_DIV=16"],
-    "kd32": ["RT_KNN_DIV=32"],
     "wf5": ["RT_WF_WAVES=5"],                  # level-synchronous kernels at 5 / 3 waves per SIMD
     "wf3": ["RT_WF_WAVES=3"],
-    "head": [],                                # a copy of the in-tree library (the A of an A/B)
-    "flate": [],                               # shade_node's local colour stored into the frame only when it pushes
-    "reslds": [],                              # a finished sample's colour waits in LDS, not in spilled VGPRs
-    "reslds0": ["RT_RES_LDS=0"],
-    "inner0": ["RT_KNN_INNER=0"],             # the kNN final pass scans every photon below the window (round 4)
-    "sprim0": ["RT_SPRIM=0"],                 # top-level implicit primitives as vector loads (round 4)
-    "sprim1": ["RT_SPRIM=1"],                 # ... as scalar loads in the variants without a photon map
-    "sprim2": ["RT_SPRIM=2"],                 # ... in every variant
-    "uload0": ["RT_ULOAD=0"],                 # leaf transforms / light fields as per-lane loads
-    "uload1": ["RT_ULOAD=1"],                 # the leaf member's transform inverse as scalar loads
-    "uload2": ["RT_ULOAD=2"],                 # the light's spot / disk fields as scalar loads
-    "uload3": ["RT_ULOAD=3"],
-    "ex0": ["RT_KNN_EXTRAP=0"],               # kNN start window too small: widen to the node's far corner
-    "ex1": ["RT_KNN_EXTRAP=1"],               # ... to the density extrapolation, above the counted photons
-    "ex1s115": ["RT_KNN_EXTRAP=1", "RT_KNN_START=1.15"],
-    "ex1s10": ["RT_KNN_EXTRAP=1", "RT_KNN_START=1.0"],
-    "ex1s11": ["RT_KNN_EXTRAP=1", "RT_KNN_START=1.1"],
-    "ex1s12": ["RT_KNN_EXTRAP=1", "RT_KNN_START=1.2"],
-    "ex1s125": ["RT_KNN_EXTRAP=1", "RT_KNN_START=1.25"],
-    "h8off": ["RT_KNN_H8=0"],                 # kNN counting: 64 u16 LDS buckets (round 2)
-    "h8on": ["RT_KNN_H8=1"],                  # 128 u8 buckets, u16 pass on a carry
-    "h8s12": ["RT_KNN_H8=1", "RT_KNN_START=1.2"],
-    "h8s13": ["RT_KNN_H8=1", "RT_KNN_START=1.3"],
-    "slim0": ["RT_FRAME_SLIM=0"],             # shading-tree frames with every field (round 4)
-    "slim1": ["RT_FRAME_SLIM=1"],             # ... without the fields derivable at the fold
-    "xh0": ["RT_XCD_HASH=0"],                 # longest-first tile order, blocks dealt to XCDs as they come
-    "xh2": ["RT_XCD_HASH=2"],                 # 2x2-tile superblocks hashed to one XCD's list
-    "xh4": ["RT_XCD_HASH=4"],
-    "xh8": ["RT_XCD_HASH=8"],
-    "sc0": ["RT_SLAB_CALL=0"],                # exact slab fallback inlined in the traversal loops
-    "sc1": ["RT_SLAB_CALL=1"],                # ... as a real call
-    "apx0": ["RT_APX2=0"],                    # approximate box test returning a tri-state int
-    "apx1": ["RT_APX2=1"],                    # ... as two lane masks (settled, hit)
-    "ib0": ["RT_INV_BALLOT=0"],               # a lane's bit of a wave mask by shift and compare
-    "ib1": ["RT_INV_BALLOT=1"],               # ... by inverse ballot (the mask as exec)
-    "ib1apx1": ["RT_INV_BALLOT=1", "RT_APX2=1"],
-    "mo0": ["RT_MASKOPS=0"],                  # packet lane bits by shift, tri-state approximate box tests
-    "mo1": ["RT_MASKOPS=1"],                  # inverse ballot + lane-mask box tests in opaque variants (default)
-    "tl0": [],                                # (the default build)
-    "tlsum": ["RT_SUMS_LDS_TRANS=1"],         # per-pixel sums in LDS in the transparent variants
-    "tlres": ["RT_RES_LDS_TRANS=1"],          # finished colours in LDS in the transparent variants
-    "tlboth": ["RT_SUMS_LDS_TRANS=1", "RT_RES_LDS_TRANS=1"],
-    "fin": [],                                # the final build's settings (A of the last A/Bs)
-    "mo2": ["RT_MASKOPS=2"],                  # mask ops in every variant
-    "mo2xh4": ["RT_MASKOPS=2", "RT_XCD_HASH=4"],
-    "lb0": ["RT_NF_LB=0"],                    # nearest-first: grown-box entry by its own slab computation
-    "lb1": ["RT_NF_LB=1"],                    # ... as a lower bound from the exact box's slab values
-    "kd0": ["RT_KNN_DIV=0"],                  # kNN scans as packets only
-    "uo0": ["RT_UNI_OPAQUE=0"],               # uniform values hoisted (and spilled) out of the sample loop (round 5)
-    "uo1": [],                                # ... made opaque where used (uni_here, default)
-    "f320": ["RT_F32_BOX=0"],                 # box tests in fp64 only (round 5)
-    "f32nf": ["RT_F32_SHADOW=0"],             # fp32 box pre-test in the nearest-first closest hit only
-    "f32all": ["RT_F32_SHADOW_OPAQUE=1"],     # ... and in every variant's shadow traversal
-    "f32def": [],                             # ... in the transparent variants' shadow traversal (default)
-    "f32nt": ["RT_F32_SHADOW_TRANS=0"],       # ... but not in the transparent variants' shadow traversal
-    "lz0": ["RT_F32_SH_LAZY=0"],              # shadow fp32 pre-test with the fp32 ray held through the traversal
-    "lz": [],                                 # ... rebuilt per node from the fp64 ray (default)
-    "lzop": ["RT_F32_SHADOW_OPAQUE=1"],       # ... and in the opaque variants' (C3's) shadow traversal too
-    "cpk0": ["RT_F32_CPK=0"],                 # reference-order closest hit (transparent variants): fp64 box tests
-    "cpk": [],                                # ... with the fp32 pre-test (default)
-    "cpkph0": ["RT_F32_CPK_PHOTON=0"],        # ... but not in the photon-map variant
-    "tri0": ["RT_F32_TRI=0"],                 # no fp32 triangle edge pre-test
-    "tricpk0": ["RT_F32_TRI_CPK=0"],          # ... none in the reference-order closest hit
-    "tph01": ["RT_F32_TRI_PH_ANY=0", "RT_F32_TRI_PH_CPK=1"],  # photon variant: the triangle pre-test in its closest hit
-    "tph11": ["RT_F32_TRI_PH_ANY=1", "RT_F32_TRI_PH_CPK=1"],  # ... in both traversals
     "nosample": ["RT_PROF_NOSAMPLE"],         # camera setup, sums and output alone (results differ)
-    "wf0": ["RT_WAVE_FAST=0"],                # wave prologue / sums as before: divisions, one summing lane, / n
-    "wf0ns": ["RT_WAVE_FAST=0", "RT_PROF_NOSAMPLE"],
-    "pers": ["RT_PERSIST=1"],                 # persistent render launches: resident grid, tiles from a ticket counter
     # known normalisations: each part off, and all four off (the statements as they were)
     "ru0": ["RT_RENORM_UNIT=0"], "dw0": ["RT_HIT_DW=0"], "ld0": ["RT_LIGHT_DIST=0"], "ps0": ["RT_PLANAR_SIGN=0"],
     "kn0": ["RT_RENORM_UNIT=0", "RT_HIT_DW=0", "RT_LIGHT_DIST=0", "RT_PLANAR_SIGN=0"],
@@ -172,8 +79,7 @@ VARIANTS = {  # name -> -D defines; names like "s12w4" are parsed (see defines_o
     "c4mr": ["@trace.hip:-Xarch_device", "@trace.hip:-mllvm=--amdgpu-sched-strategy=iterative-minreg",
              "@trace.hip:-Xarch_device", "@trace.hip:-mllvm=--amdgpu-use-amdgpu-trackers=1"],
 }
-FIELDS = {"w": "RT_RENDER_WAVES", "s": "RT_STACK_LDS", "x": "RT_XCD_CHUNKS", "g": "RT_MAX_G", "p": "RT_PACKET",
-          "l": "RT_PK_LDS", "b": "RT_PH_BATCH", "m": "RT_PK_MASKED"}
+FIELDS = {"w": "RT_RENDER_WAVES", "s": "RT_STACK_LDS", "g": "RT_MAX_G", "l": "RT_PK_LDS", "b": "RT_PH_BATCH"}
 
 
 def defines_of(name: str) -> list[str]:

@@ -26,6 +26,16 @@ shading branches the sky pin (tests/test_refpin.py) cannot reach:
               myTextureHandler.java:84-117; mySphere.findTextureU/V, myImpObject.java:97-122)
   kat_photon  a photon irradiance at k = 5 over hand-placed photons (getIrradianceFromPhtnTree,
               myObjShader.java:441-458; find_near, myLight.java:389-445)
+  kat_noise, kat_wood, kat_wood2, kat_marble, kat_stone_euclid, kat_stone_manhattan
+              the procedural texture handlers (myTextureHandler.java:178-680), six pixels a scene chosen to
+              take every branch (TEX_KATS): noise_3d with every operation rounded to float32
+              (DistRayTracer.java:234-310), getNoiseVal / getTurbVal / getAbsTurbVal, getClrAra with its
+              permuted noise arguments, the wood, wood2 and marble bands, the Worley texture with its
+              per-cell java.util.Random, pdf table and lowerKey lookup, the nine ROI functions and both
+              distance functions, noise_color (numeric, named, and its order relative to the texture
+              command) and the argument parsers with their defaults and short forms (myScene.java:571-777).
+              Written from the Java alone; tests/test_textures.py holds it against the oracle in breadth
+              and shows that it tells the Java's reading from nine near misreadings
 
 The first five scenes have identity transforms; the classes below keep the reference's mutable state
 (the in-place re-normalisation of a ray's direction in getTransformedRay, myRay.java:93; the
@@ -326,6 +336,7 @@ class Shader:
         self.has_caustic = (krefl > 0.0) or (perm > 0.0) or (ktrans > 0.0)  # setCurrColors :69
         self.diff_const = 1 - perm                                            # :73
         self.tex = None            # the image texture (`texture` before the shader's object), RGB rows
+        self.proc = None           # a ProcTexture (noise / wood / wood2 / marble / stone before the object)
         self.use_photons = False   # shdrFlags[usePhotonMap]: a photon command before the shader
 
 
@@ -620,6 +631,420 @@ class BVH:
         return False
 
 
+# ---- procedural textures (myTextureHandler.java:178-680, DistRayTracer.java:21-29,232-310)
+_F32 = struct.Struct("f")
+
+
+def f32(x):
+    """A Java `float` result: the double-precision value of one operation on floats, rounded to
+    float32 (exact for + - * of two floats: 53 >= 2 * 24 + 2 bits), and the `(float)` cast."""
+    return _F32.unpack(_F32.pack(x))[0]
+
+
+def i32(v):  # Java int arithmetic wraps
+    v &= 0xFFFFFFFF
+    return v - (1 << 32) if v >= (1 << 31) else v
+
+
+def fastfloor(x):  # DistRayTracer.fastfloor (:306-307): x > 0 ? (int) x : (int) x - 1 (so 0 and -2.0 go one lower)
+    return int(x) if x > 0 else int(x) - 1
+
+
+GRAD3 = ((1, 1, 0), (-1, 1, 0), (1, -1, 0), (-1, -1, 0), (1, 0, 1), (-1, 0, 1), (1, 0, -1), (-1, 0, -1), (0, 1, 1),
+         (0, -1, 1), (0, 1, -1), (0, -1, -1))                                       # :287
+PERLIN_P = (151, 160, 137, 91, 90, 15, 131, 13, 201, 95, 96, 53, 194, 233, 7, 225, 140, 36, 103, 30, 69, 142, 8, 99,
+            37, 240, 21, 10, 23, 190, 6, 148, 247, 120, 234, 75, 0, 26, 197, 62, 94, 252, 219, 203, 117, 35, 11, 32,
+            57, 177, 33, 88, 237, 149, 56, 87, 174, 20, 125, 136, 171, 168, 68, 175, 74, 165, 71, 134, 139, 48, 27,
+            166, 77, 146, 158, 231, 83, 111, 229, 122, 60, 211, 133, 230, 220, 105, 92, 41, 55, 46, 245, 40, 244, 102,
+            143, 54, 65, 25, 63, 161, 1, 216, 80, 73, 209, 76, 132, 187, 208, 89, 18, 169, 200, 196, 135, 130, 116,
+            188, 159, 86, 164, 100, 109, 198, 173, 186, 3, 64, 52, 217, 226, 250, 124, 123, 5, 202, 38, 147, 118, 126,
+            255, 82, 85, 212, 207, 206, 59, 227, 47, 16, 58, 17, 182, 189, 28, 42, 223, 183, 170, 213, 119, 248, 152,
+            2, 44, 154, 163, 70, 221, 153, 101, 155, 167, 43, 172, 9, 129, 22, 39, 253, 19, 98, 108, 110, 79, 113, 224,
+            232, 178, 185, 112, 104, 218, 246, 97, 228, 251, 34, 242, 193, 238, 210, 144, 12, 191, 179, 162, 241, 81,
+            51, 145, 235, 249, 14, 239, 107, 49, 192, 214, 31, 181, 199, 106, 157, 184, 84, 204, 176, 115, 121, 50, 45,
+            127, 4, 150, 254, 138, 236, 205, 93, 222, 114, 67, 29, 24, 72, 243, 141, 128, 195, 78, 66, 215, 61, 156,
+            180)                                                                    # Ken Perlin's table, :288-300
+PERM = tuple(PERLIN_P[i & 255] for i in range(512))                                 # initialize_table :304
+assert sorted(PERLIN_P) == list(range(256))
+
+
+def _gdot(g, x, y, z):  # dot (:308): g[0]*x + g[1]*y + g[2]*z, ints widened to float, left to right
+    return f32(f32(f32(g[0] * x) + f32(g[1] * y)) + f32(g[2] * z))
+
+
+def _fade(t):  # fade (:310): t*t*t*(t*(t*6-15)+10)
+    return f32(f32(f32(t * t) * t) * f32(f32(t * f32(f32(t * 6.0) - 15.0)) + 10.0))
+
+
+def _mix(a, b, t):  # mix (:309): (1-t)*a + t*b
+    return f32(f32(f32(1.0 - t) * a) + f32(t * b))
+
+
+def noise3(x, y, z):
+    """noise_3d(float, float, float) (:234-284): every operation a float operation. The arguments
+    are float32 values already (the callers' `(float)` casts)."""
+    X, Y, Z = fastfloor(x), fastfloor(y), fastfloor(z)                              # :238
+    x, y, z = f32(x - f32(X)), f32(y - f32(Y)), f32(z - f32(Z))                     # :240
+    X, Y, Z = X & 255, Y & 255, Z & 255                                             # :242 (two's complement)
+    gi000 = PERM[X + PERM[Y + PERM[Z]]] % 12                                        # :244-251
+    gi001 = PERM[X + PERM[Y + PERM[Z + 1]]] % 12
+    gi010 = PERM[X + PERM[Y + 1 + PERM[Z]]] % 12
+    gi011 = PERM[X + PERM[Y + 1 + PERM[Z + 1]]] % 12
+    gi100 = PERM[X + 1 + PERM[Y + PERM[Z]]] % 12
+    gi101 = PERM[X + 1 + PERM[Y + PERM[Z + 1]]] % 12
+    gi110 = PERM[X + 1 + PERM[Y + 1 + PERM[Z]]] % 12
+    gi111 = PERM[X + 1 + PERM[Y + 1 + PERM[Z + 1]]] % 12
+    x1, y1, z1 = f32(x - 1.0), f32(y - 1.0), f32(z - 1.0)
+    n000 = _gdot(GRAD3[gi000], x, y, z)                                             # :257-264
+    n100 = _gdot(GRAD3[gi100], x1, y, z)
+    n010 = _gdot(GRAD3[gi010], x, y1, z)
+    n110 = _gdot(GRAD3[gi110], x1, y1, z)
+    n001 = _gdot(GRAD3[gi001], x, y, z1)
+    n101 = _gdot(GRAD3[gi101], x1, y, z1)
+    n011 = _gdot(GRAD3[gi011], x, y1, z1)
+    n111 = _gdot(GRAD3[gi111], x1, y1, z1)
+    u, v, w = _fade(x), _fade(y), _fade(z)                                          # :267
+    return _mix(_mix(_mix(n000, n100, u), _mix(n010, n110, u), v),
+                _mix(_mix(n001, n101, u), _mix(n011, n111, u), v), w)               # :282
+
+
+FREQ_STEP = 1.92  # getTurbVal / getAbsTurbVal's "_freqScale *= 1.92" (myTextureHandler.java:237,248)
+
+
+def turb_val(p, octaves, absolute):
+    """getTurbVal (:231-240) / getAbsTurbVal (:242-251) of the already scaled point p: the products in
+    double, cast to float per coordinate; the noise widened back to double."""
+    res, freq, amp = 0.0, 1.0, 1.0
+    for _ in range(octaves):
+        n = noise3(f32(p[0] * freq), f32(p[1] * freq), f32(p[2] * freq))
+        res += (abs(n) if absolute else n) * amp
+        amp *= .5
+        freq *= FREQ_STEP
+    return res
+
+
+# getClrAra's three noise calls read the point as (x, z, y), (y, x, z), (z, y, x) (:283-285)
+CLR_NOISE_ARGS = ((0, 2, 1), (1, 0, 2), (2, 1, 0))
+
+NAMED_COLORS = {  # DistRayTracer.getClr (:467-528); clr_rnd (Processing's unseeded random) is not restated
+    "clr_gray": (0.47, 0.47, 0.47), "clr_white": (1.0, 1.0, 1.0), "clr_yellow": (1.0, 1.0, 0), "clr_cyan": (0, 1.0, 1.0),
+    "clr_magenta": (1.0, 0, 1.0), "clr_red": (1.0, 0, 0), "clr_blue": (0, 0, 1.0), "clr_purple": (0.6, 0.2, 1.0),
+    "clr_green": (0, 1.0, 0), "clr_ltwood1": (0.94, 0.47, 0.12), "clr_ltwood2": (0.94, 0.8, 0.4),
+    "clr_dkwood1": (0.2, 0.08, 0.08), "clr_dkwood2": (0.3, 0.20, 0.16), "clr_mortar1": (0.2, 0.2, 0.2),
+    "clr_mortar2": (0.7, 0.7, 0.7), "clr_brick1_1": (0.6, 0.18, 0.22), "clr_brick1_2": (0.8, 0.26, 0.33),
+    "clr_brick2_1": (0.6, 0.32, 0.16), "clr_brick2_2": (0.8, 0.45, 0.25), "clr_brick3_1": (0.3, 0.01, 0.07),
+    "clr_brick3_2": (0.6, 0.02, 0.13), "clr_brick4_1": (0.4, 0.1, 0.17), "clr_brick4_2": (0.6, 0.3, 0.13),
+    "clr_darkgray": (0.31, 0.31, 0.31), "clr_darkred": (0.47, 0, 0), "clr_darkblue": (0, 0, 0.47),
+    "clr_darkpurple": (0.4, 0.2, 0.6), "clr_darkgreen": (0, 0.47, 0), "clr_darkyellow": (0.47, 0.47, 0),
+    "clr_darkmagenta": (0.47, 0, 0.47), "clr_darkcyan": (0, 0.47, 0.47), "clr_lightgray": (0.78, 0.78, 0.78),
+    "clr_lightred": (1.0, .43, .43), "clr_lightblue": (0.43, 0.43, 1.0), "clr_lightgreen": (0.43, 1.0, 0.43),
+    "clr_lightyellow": (1.0, 1.0, .43), "clr_lightmagenta": (1.0, .43, 1.0), "clr_lightcyan": (0.43, 1.0, 1.0),
+    "clr_black": (0, 0, 0), "clr_nearblack": (0.05, 0.05, 0.05), "clr_faintgray": (0.43, 0.43, 0.43),
+    "clr_faintred": (0.43, 0, 0), "clr_faintblue": (0, 0, 0.43), "clr_faintgreen": (0, 0.43, 0),
+    "clr_faintyellow": (0.43, 0.43, 0), "clr_faintcyan": (0, 0.43, 0.43), "clr_faintmagenta": (0.43, 0, 0.43),
+    "clr_offwhite": (0.95, 0.98, 0.92)}
+
+
+def named_color(name):  # getClr: lower-cased; an unknown name is white (:528)
+    return clamp_color(*[float(c) for c in NAMED_COLORS.get(name.lower(), (1.0, 1.0, 1.0))])
+
+
+class JRandom:
+    """java.util.Random: setSeed's scrambling, the 48-bit LCG of next(bits), nextDouble from 26 + 27 bits."""
+    MASK = (1 << 48) - 1
+
+    def set_seed(self, s):  # the int seed widens to long (sign-extended); (seed ^ 0x5DEECE66DL) & mask
+        self.seed = (s ^ 0x5DEECE66D) & self.MASK
+
+    def next(self, bits):  # (int) (seed >>> (48 - bits))
+        self.seed = (self.seed * 0x5DEECE66D + 0xB) & self.MASK
+        return i32(self.seed >> (48 - bits))
+
+    def next_double(self):  # (((long) next(26) << 27) + next(27)) * 0x1.0p-53
+        return ((self.next(26) << 27) + self.next(27)) * 2.0 ** -53
+
+
+NGHBR = ((0, 0, 0), (0, 0, 1), (0, 0, -1), (0, 1, 0), (0, 1, 1), (0, 1, -1), (0, -1, 0), (0, -1, 1), (0, -1, -1),
+         (1, 0, 0), (1, 0, 1), (1, 0, -1), (1, 1, 0), (1, 1, 1), (1, 1, -1), (1, -1, 0), (1, -1, 1), (1, -1, -1),
+         (-1, 0, 0), (-1, 0, 1), (-1, 0, -1), (-1, 1, 0), (-1, 1, 1), (-1, 1, -1), (-1, -1, 0), (-1, -1, 1),
+         (-1, -1, -1))                                                              # nghbrHdCells (DistRayTracer.java:21-25)
+
+
+def hash_ints(x, y, z):  # hashInts (:438) with hashPrime1 / hashPrime2 (DistRayTracer.java:28-29), int arithmetic
+    return i32(x * 1572869 + y * 6291469 + z)
+
+
+def pdf_table(avg):
+    """The cumulative Poisson table of the myCellularTexture ctor (:424-432): key i = P(N <= i), for
+    i = 1 .. 14; P(N = 0) is accumulated but never put, and equal keys keep the later i (Map.put)."""
+    last = 1.0 / math.pow(math.e, avg)
+    cum = last
+    table = {}
+    for i in range(1, 15):
+        last *= (avg / (1.0 * i))
+        cum += last
+        table[cum] = i
+    return table
+
+
+def lower_key(keys, x):  # ConcurrentSkipListMap.lowerKey: the greatest key strictly below x, or None
+    best = None
+    for k in keys:
+        if k < x and (best is None or k > best):
+            best = k
+    return best
+
+
+def num_points(table, prob):  # :458: pdfs.get(null == lowerKey(prob) ? firstKey() : lowerKey(prob)): never 0
+    k = lower_key(table, prob)
+    return table[min(table) if k is None else k]
+
+
+def l1_dist(a, b):  # myVector._L1Dist (myVector.java:36)
+    return abs(a[0] - b[0]) + abs(a[1] - b[1]) + abs(a[2] - b[2])
+
+
+DIST_FUNCS = {0: l1_dist, 1: dist}  # :418-422: 0 manhatDist, 1 and anything else euclidDist (_dist, myVector.java:37)
+
+
+def fix_dist(d):  # myROI.fixDist (:520-524)
+    if d < 0:
+        d *= -1
+    if d > 1.0:
+        d = 1.0 / d
+    return d
+
+
+# the nine myROI.calcROI bodies (:527-680): (term of the i-th smallest distance, i counted from 1;
+# whether the sign alternates from -1; whether fixDist is applied -- linLogROI :642 returns its bare sum)
+ROI_FUNCS = {
+    0: (lambda d, i: d, False, True),                          # nearestROI :530-535
+    1: (lambda d, i: d, True, True),                           # altLinROI :543-553
+    2: (lambda d, i: 1.0 / d, True, True),                     # altInvLinROI :562-572: 1.0 / (modVal * d)
+    3: (lambda d, i: math.pow(d, i), True, True),              # altExpROI :581-590
+    4: (lambda d, i: math.log(1 + d), True, True),             # altLogROI :599-609
+    5: (lambda d, i: math.pow(d, i), False, True),             # linExpROI :617-625
+    6: (lambda d, i: math.log(1 + d), False, False),           # linLogROI :634-643
+    7: (lambda d, i: math.pow(d, -i), False, True),            # invExpROI :651-659
+    8: (lambda d, i: 1.0 / math.log(1 + d), False, True),      # invLogROI :668-677
+}
+
+
+def calc_roi(fn, num_pts, keys):
+    """roiFunc.calcROI(orderedKeys): the first numPtsDist of the ascending distinct distances; an
+    unknown function number is altLinROI (:416). modVal * term and 1.0 / (modVal * d) are the same
+    doubles as -term / term (a sign flip is exact)."""
+    term, alternates, fixed = ROI_FUNCS.get(fn, ROI_FUNCS[1])
+    total, mod, i = 0.0, -1, 0
+    for d in keys:
+        i += 1
+        t = term(d, i)
+        total += (mod * t) if alternates else t
+        if i >= num_pts:
+            break
+        mod *= -1
+    return fix_dist(total) if fixed else total
+
+
+def brick_cell(hit_cell, nearest_cell):  # :475: the cell stored with the smallest distance, not the hit's own
+    return nearest_cell
+
+
+def wood_color_point(h, scaled):  # myBaseWoodTexture :323 passes hit.hitLoc: object space, unscaled
+    return h.hit_loc
+
+
+class TextureState:
+    """The texture fields of myScene that setTexture / setNoise / setTxtrColor write and a texture
+    handler's constructor copies (myScene.java:571-777)."""
+
+    def __init__(self):
+        self.type = 0
+        self.use_cust = False
+        self.reset()
+
+    def reset(self):  # resetDfltTxtrVals (:579-586) -> setProcTxtrVals (:594-601)
+        self.type, self.octaves, self.num_pts, self.dist_func, self.roi_func = 0, 4, 2, 1, 1
+        self.rnd_colors, self.use_cust, self.use_fwd = False, False, False
+        self.scale, self.turb, self.color_scale, self.color_mult, self.avg, self.mortar = 1.0, 1.0, 5.0, .1, 1.0, 0.05
+        self.pd = [1.0, 1.0, 1.0]
+        self.colors = [named_color("clr_nearblack"), named_color("clr_white")]
+
+    def _short_form(self, v, k):  # :658-666 / :689-697: colour scale and multiplier both, or neither
+        try:
+            self.color_scale, self.color_mult = float(v[k]), float(v[k + 1])
+            self.rnd_colors = True
+        except (ValueError, IndexError):
+            self.rnd_colors, self.color_scale, self.color_mult = False, 25.0, .1
+
+    def read_perlin(self, v):  # readProcTxtrPerlinVals (:642-672); True: use the kind's defaults
+        try:
+            self.scale, self.octaves, self.turb = float(v[1]), int(v[2]), float(v[3])
+            self.pd = [float(v[4]), float(v[5]), float(v[6])]
+            py = [float(v[7]), float(v[8]), float(v[9])]
+            if ((py[0] * py[0]) + (py[1] * py[1])) + (py[2] * py[2]) > 0:  # sqMagn :652
+                py = [(c * (FLOAT_TWO_PI - 1.0)) + 1.0 for c in py]        # 0|1 -> 1|2 pi (:653-654)
+                self.pd = [self.pd[0] * py[0], self.pd[1] * py[1], self.pd[2] * py[2]]
+            self.use_fwd = (float(v[10]) == 1.0)
+            self._short_form(v, 11)
+            return False
+        except (ValueError, IndexError):
+            return True
+
+    def read_worley(self, v):  # readProcTxtrWorleyVals (:675-703)
+        try:
+            self.scale, self.dist_func, self.roi_func, self.num_pts = float(v[1]), int(v[2]), int(v[3]), int(v[4])
+            self.avg, self.mortar = float(v[5]), float(v[6])
+            self.use_fwd = (float(v[7]) == 1.0)
+            self._short_form(v, 8)
+            return False
+        except (ValueError, IndexError):
+            return True
+
+    def _defaults(self, octaves, scale, turb, color_scale, color_mult, pd):
+        """The useDefaults branch's setProcTxtrVals (:723-728 and its siblings): everything but the type
+        and the colours; rndColors true, useFwdTrans false, numPtsDist 2, distFunc 1, roiFunc 1."""
+        self.octaves, self.num_pts, self.dist_func, self.roi_func = octaves, 2, 1, 1
+        self.rnd_colors, self.use_fwd = True, False
+        self.scale, self.turb, self.color_scale, self.color_mult, self.avg, self.mortar = scale, turb, color_scale, color_mult, 1.0, 0.05
+        self.pd = list(pd)
+
+    def set_texture(self, v):  # setTexture (:712-777)
+        self.reset()  # :714 -- which forgets every noise_color given before this command
+        kind = v[0]
+        if kind == "wood":
+            self.type = 3
+            dflt = self.read_perlin(v)
+            if not self.use_cust:
+                self.colors = [named_color("clr_dkwood1"), named_color("clr_ltwood1")]
+            if dflt:
+                self._defaults(4, 2.0, .4, 25.0, .2, (FLOAT_TWO_PI * 2.7, 3.6, 4.3))
+        elif kind == "wood2":
+            self.type = 6
+            dflt = self.read_perlin(v)
+            if not self.use_cust:
+                self.colors = [named_color("clr_dkwood2"), named_color("clr_ltwood2")]
+            if dflt:
+                self._defaults(8, 1.0, .4, 25.0, .3, (FLOAT_TWO_PI * 3.5, 7.9, 6.2))
+        elif kind == "marble":
+            self.type = 4
+            dflt = self.read_perlin(v)
+            if not self.use_cust:
+                self.colors = [named_color("clr_nearblack"), named_color("clr_offwhite")]
+            if dflt:
+                self._defaults(16, 1.0, 15.0, 24.0, .1, (FLOAT_TWO_PI * 0.1, FLOAT_TWO_PI * 31.4, FLOAT_TWO_PI * 4.1))
+        elif kind == "stone":
+            self.type = 5
+            dflt = self.read_worley(v)
+            if not self.use_cust:
+                self.colors = [named_color(n) for n in (
+                    "clr_mortar1", "clr_mortar2", "clr_brick1_1", "clr_brick1_2", "clr_brick2_1", "clr_brick2_2",
+                    "clr_brick3_1", "clr_brick3_2", "clr_brick4_1", "clr_brick4_2")]
+            if dflt:
+                self._defaults(8, 4.0, 1.0, 12.0, .2, (10.0, 10.0, 10.0))
+        else:
+            raise ValueError(kind)
+
+    def set_noise(self, v):  # setNoise (:571-576)
+        self.reset()
+        self.type = 2
+        self.scale = float(v[1])
+
+    def add_color(self, v):
+        """setTxtrColor (:604-639): the first noise_color after a texture command empties the list. The
+        weights are read but no handler uses them for a colour."""
+        if not self.use_cust:
+            self.colors = []
+            self.use_cust = True
+        if v[1] == "named":
+            self.colors.append(named_color(v[2]))
+        else:
+            self.colors.append(clamp_color(float(v[1]), float(v[2]), float(v[3])))   # readColor, myColor ctor
+
+
+class ProcTexture:
+    """myNoiseTexture and its subclasses, built by getCurTexture (myScene.java:531-542) from the
+    scene's texture fields as they stand when an object is created (initTextureVals :200-209)."""
+
+    def __init__(self, ts):
+        self.type, self.scale, self.octaves, self.turb = ts.type, ts.scale, ts.octaves, ts.turb
+        self.pd = list(ts.pd)
+        self.color_scale, self.color_mult, self.rnd_colors, self.use_fwd = ts.color_scale, ts.color_mult, ts.rnd_colors, ts.use_fwd
+        self.colors = [list(c) for c in ts.colors]
+        if ts.type == 5:  # myCellularTexture ctor :400-436
+            self.avg, self.mortar, self.num_pts, self.roi_func, self.dist_func = ts.avg, ts.mortar, ts.num_pts, ts.roi_func, ts.dist_func
+            self.pdf = pdf_table(ts.avg)
+
+    def hit_loc(self, h):  # getHitLoc :254
+        return list(h.fwd_hit) if self.use_fwd else list(h.hit_loc)
+
+    def clr_ara(self, dist_val, raw_pt, i0, i1):  # getClrAra :277-294
+        pt = [raw_pt[0] * self.color_scale, raw_pt[1] * self.color_scale, raw_pt[2] * self.color_scale]
+        rm = [1.0, 1.0, 1.0]
+        if self.rnd_colors:
+            rm = [1.0 + (self.color_mult * noise3(f32(pt[a]), f32(pt[b]), f32(pt[c]))) for a, b, c in CLR_NOISE_ARGS]
+        c0, c1 = self.colors[i0], self.colors[i1]
+        raw = [c0[k] + rm[k] * dist_val * (c1[k] - c0[k]) for k in range(3)]
+        TRACE.append(("clr_clamp", [-1 if v < 0 else (1 if v > 1.0 else 0) for v in raw]))
+        return [max(0.0, min(1.0, v)) for v in raw]
+
+    def sq_pt_val(self, p):  # sqPtVal :275
+        return math.sqrt((p[0] * p[0]) * self.pd[0] + (p[1] * p[1]) * self.pd[1] + (p[2] * p[2]) * self.pd[2])
+
+    def color(self, h):
+        p = self.hit_loc(h)
+        p = [p[0] * self.scale, p[1] * self.scale, p[2] * self.scale]  # every handler scales hitVal in place first
+        TRACE.append(("proc", self.type, p))
+        pm_mag = mag(self.pd)                                          # periodMult._mag()
+        if self.type == 2:    # myNoiseTexture.getDiffTxtrColor :257-265
+            val = .5 * (self.turb * noise3(f32(p[0]), f32(p[1]), f32(p[2]))) + .5
+            return [val, val, val]
+        if self.type == 3:    # myBaseWoodTexture :312-328: one noise value, sqPtVal of the scaled point
+            res = noise3(f32(p[0]), f32(p[1]), f32(p[2]))
+            d = math.sin((self.sq_pt_val(p) + self.turb * res) * pm_mag)
+            d *= 1.1
+            d += .5
+            TRACE.append(("wood_clamp", -1 if d < 0 else (1 if d > 1 else 0)))
+            d = 0 if d < 0 else (1 if d > 1 else d)
+            return self.clr_ara(d, wood_color_point(h, p), 0, 1)
+        if self.type == 6:    # myWoodTexture :341-352
+            res = turb_val(p, self.octaves, False)
+            d = math.sin((self.sq_pt_val(p) + self.turb * res) * pm_mag)
+            TRACE.append(("wood2_clamp", d < 0))
+            d = 1 - (0 if d < 0 else d)
+            return self.clr_ara(d, p, 0, 1)
+        if self.type == 4:    # myMarbleTexture :366-377, linPtVal :274
+            res = turb_val(p, self.octaves, True)
+            spt = (p[0] * self.pd[0] + p[1] * self.pd[1] + p[2] * self.pd[2]) / pm_mag + self.turb * res
+            return self.clr_ara(.5 * math.sin(spt) + .5, p, 0, 1)
+        return self.stone(p)
+
+    def stone(self, p):  # myCellularTexture.getDiffTxtrColor :445-487
+        idx = [fastfloor(p[0]), fastfloor(p[1]), fastfloor(p[2])]                   # :449
+        dist_to = {}                      # distToPts: an equal distance replaces the stored cell
+        rnd = JRandom()
+        fn = DIST_FUNCS.get(self.dist_func, DIST_FUNCS[1])
+        for n in NGHBR:                                                             # :453-465
+            cell = (idx[0] + n[0], idx[1] + n[1], idx[2] + n[2])
+            rnd.set_seed(hash_ints(*cell))
+            for _ in range(num_points(self.pdf, rnd.next_double())):
+                px = cell[0] + rnd.next_double()
+                py = cell[1] + rnd.next_double()
+                pz = cell[2] + rnd.next_double()
+                dist_to[fn(p, [px, py, pz])] = cell
+        keys = sorted(dist_to)
+        d = calc_roi(self.roi_func, self.num_pts, keys)                             # :468
+        d = 0 if d < 0 else (1 if d > 1 else d)                                     # :469
+        if d < self.mortar:                                                         # :472
+            brick = 0
+        else:
+            c0 = brick_cell(tuple(idx), dist_to[keys[0]])                           # :475-479
+            rnd.set_seed(hash_ints(*c0))
+            brick = 2 * (1 + fastfloor(((len(self.colors) // 2) - 1) * rnd.next_double()))   # :480
+        TRACE.append(("stone", brick, d, len(keys)))
+        return self.clr_ara(.65, p, brick, brick + 1)                               # :482
+
+
 # ---- lights (myLight.java)
 class Light:
     def __init__(self, kind, index, origin, color, orient=(0.0, 0.0, 0.0), inner=0.0, outer=0.0, radius=0.0,
@@ -823,14 +1248,18 @@ class Scene:
         u, v = h.obj.tex_coords(h.hit_loc, tw, th)
         ui, vi = int(u), int(v)
 
-        def texel(r, c):
-            px = img[r][c]
+        flat = [px for row in img for px in row]   # PImage.pixels: row-major; the Java indexes it flat (:92), so
+        # at the last column idx + 1 is the next row's first texel. Past either end the Java throws; the
+        # product clamps the index there, and so does this.
+
+        def texel(i):
+            px = flat[min(max(i, 0), len(flat) - 1)]
             return [px[0] / 255.0, px[1] / 255.0, px[2] / 255.0]
 
         def interp(a, t, b):  # myColor.interpColor (myObjShader.java:667): clamped <= 1
             return clamp_color(a[0] + t * (b[0] - a[0]), a[1] + t * (b[1] - a[1]), a[2] + t * (b[2] - a[2]))
-        c00, c10 = texel(vi, ui), texel(vi + 1, ui)
-        c01, c11 = texel(vi, ui + 1), texel(vi + 1, ui + 1)
+        i00 = vi * tw + ui
+        c00, c10, c01, c11 = texel(i00), texel(i00 + tw), texel(i00 + 1), texel(i00 + tw + 1)
         fu, fv = u - ui, v - vi
         return interp(interp(c00, fu, c01), fv, interp(c10, fu, c11))
 
@@ -841,7 +1270,12 @@ class Scene:
             irr = self.irradiance(h.fwd_hit)
             r += sh.diff[0] * irr[0]; g += sh.diff[1] * irr[1]; b += sh.diff[2] * irr[2]
         dc = 1.0 if sh.simple else sh.diff_const
-        base = self.tex_color(h) if sh.tex is not None else sh.diff                 # getDiffTxtrColor :105-111
+        if sh.proc is not None:    # the noise handlers multiply by diffConst only when it is not 1 (:263)
+            base = sh.proc.color(h)
+            if not abs(dc - 1.0) > EPS:
+                dc = 1.0
+        else:
+            base = self.tex_color(h) if sh.tex is not None else sh.diff             # getDiffTxtrColor :105-111
         tex = [base[0] * dc, base[1] * dc, base[2] * dc]
         s = self.shadow_color(h, tex, key)
         r += s[0]; g += s[1]; b += s[2]
@@ -867,7 +1301,7 @@ class Scene:
         return self.reflect_ray(ray, (seed, row * self.W + col, 0))
 
 
-def load(cli_text, W, H, scene_dir=None):
+def load(cli_text, W, H, scene_dir=None, textures=None):
     """The handful of .cli commands these scenes use (myRTFileReader.java:113-313). Objects take the
     matrix-stack top (myGeomBase ctor, myGeomBase.java:37) and a shader of the current settings
     (getCurShader, myScene.java:524-528: the image texture and the photon flag included)."""
@@ -877,11 +1311,13 @@ def load(cli_text, W, H, scene_dir=None):
     shader, simple_flag, poly = None, False, None
     top = IDENT                                   # matrixStack.peek()
     tex, photons = None, None                     # currTextureTop (txtrType 1) / the photon command
+    ts = TextureState()                           # txtrType and the procedural texture fields
     tmp_list = None                               # begin_list ... end_accel (addToTmpListIDX)
 
     def cur_shader():
         sh = copy.copy(shader)
-        sh.tex = tex
+        sh.tex = tex if ts.type == 1 else None    # getCurTexture (myScene.java:531-542)
+        sh.proc = ProcTexture(ts) if 2 <= ts.type <= 6 else None
         sh.use_photons = photons is not None
         return sh
 
@@ -909,13 +1345,24 @@ def load(cli_text, W, H, scene_dir=None):
             if c == "shiny" and len(tok) > 12 and (float(tok[12]) > 0 or (len(tok) > 13 and float(tok[13]) > 0)):
                 simple_flag = True  # scFlags[simpleRefrIDX] stays set for the rest of the scene (:377)
             shader = shader_from_tokens(tok, simple_flag)
+            ts.type = 0                           # setSurface (myScene.java:818): a texture command follows its material
         elif c in ("texture", "image_texture"):   # :257-272 (top texture), Pillow-decoded texels
-            from PIL import Image
             name = tok[2] if tok[1].lower() == "top" else tok[1]
-            im = Image.open(Path(scene_dir or SCENES) / "txtrs" / name).convert("RGB")
-            w, h = im.size
-            raw = im.tobytes()
-            tex = [[tuple(raw[3 * (r * w + q):3 * (r * w + q) + 3]) for q in range(w)] for r in range(h)]
+            if textures is not None and name in textures:   # an array [h][w][3] handed in place of a file
+                tex = [[tuple(int(x) for x in px) for px in row] for row in textures[name]]
+            else:
+                from PIL import Image
+                im = Image.open(Path(scene_dir or SCENES) / "txtrs" / name).convert("RGB")
+                w, h = im.size
+                raw = im.tobytes()
+                tex = [[tuple(raw[3 * (r * w + q):3 * (r * w + q) + 3]) for q in range(w)] for r in range(h)]
+            ts.type = 1                           # myRTFileReader.java:272
+        elif c == "noise":                        # myRTFileReader.java:277
+            ts.set_noise(tok)
+        elif c == "noise_color":                  # :280
+            ts.add_color(tok)
+        elif c in ("marble", "stone", "wood", "wood2"):   # :284-287
+            ts.set_texture(tok)
         elif c in ("diffuse_photons", "caustic_photons"):  # setPhotonHandling (myScene.java:919-931)
             photons = (int(tok[1]), int(tok[2]), float(tok[3]))
         elif c == "translate":                   # gtTranslate / updateCTM (myScene.java:1256-1264,1320-1323)
@@ -974,6 +1421,55 @@ KATS = [
     ("photon_irradiance_k5", "kat_photon.cli", 200, 170,
      "getIrradianceFromPhtnTree at k = 5 over hand-placed photons (distinct distances, two beyond max_dist)"),
 ]
+# One hand-written scene per procedural texture kind (tests/golden/kat_scenes/kat_<kind>.cli): the pixels were
+# chosen with tex_branches() below so that each scene's pixels together take every branch listed here --
+# scaled coordinates of both signs (fastfloor's two arms), lit and shadowed, both sides of each clamp
+# (wood's distVal, wood2's negative sine, getClrAra's max(0, min(1, .))), mortar and more than one brick pair.
+TEX_KATS = {
+    "noise": ([(102, 144), (179, 102), (102, 151), (158, 116), (172, 123), (186, 144)],
+              {"x+", "x-", "y+", "y-", "z+", "z-", "lit", "blocked"}),
+    "wood": ([(109, 144), (221, 172), (102, 179), (158, 116), (172, 123), (186, 144)],
+             {"x+", "x-", "y+", "y-", "z+", "z-", "lit", "wood<0", "wood in", "wood>1", "clr<0", "clr in", "clr>1"}),
+    "wood2": ([(102, 179), (165, 102), (144, 102), (158, 116), (172, 123), (186, 144)],
+              {"x+", "x-", "y+", "y-", "z-", "lit", "sine<0", "sine>=0", "clr<0", "clr in", "clr>1"}),
+    "marble": ([(130, 116), (179, 102), (102, 151), (158, 116), (172, 123), (186, 144)],
+               {"x+", "x-", "y+", "y-", "z+", "z-", "lit", "clr<0", "clr in", "clr>1"}),
+    "stone_euclid": ([(102, 144), (179, 102), (102, 151), (109, 144), (130, 123), (186, 144)],
+                     {"x+", "x-", "y+", "y-", "z+", "z-", "lit", "mortar", "brick 2", "brick 4", "brick 6", "brick 8"}),
+    "stone_manhattan": ([(102, 144), (221, 151), (109, 130), (109, 137), (144, 144), (186, 144)],
+                        {"x+", "x-", "y+", "y-", "z-", "lit", "mortar", "brick 2", "brick 4", "brick 6", "brick 8"}),
+}
+TEX_WHAT = {
+    "noise": "myNoiseTexture: float noise_3d of the scaled object-space hit",
+    "wood": "myBaseWoodTexture: one noise value, sqPtVal bands, colours from the unscaled hit, custom noise_color pair",
+    "wood2": "myWoodTexture: 8 octaves of getTurbVal, pi multipliers, useFwdTrans 1",
+    "marble": "myMarbleTexture: 16 octaves of getAbsTurbVal, linPtVal, a numeric and a named noise_color",
+    "stone_euclid": "myCellularTexture: Euclidean distance, altLinROI over 2 points, per-cell java.util.Random",
+    "stone_manhattan": "myCellularTexture: Manhattan distance, altLogROI over 3 points, 2 points per cell, useFwdTrans 1",
+}
+for _kind, (_px, _) in TEX_KATS.items():
+    KATS += [("%s_%d" % (_kind, _i), "kat_%s.cli" % _kind, _r, _c, TEX_WHAT[_kind]) for _i, (_r, _c) in enumerate(_px)]
+
+
+def tex_branches(path):
+    """The branches a derivation's TRACE went through in the texture code."""
+    f = set()
+    for e in path:
+        if e[0] == "proc":
+            f |= {"xyz"[k] + ("+" if e[2][k] > 0 else "-") for k in range(3)}
+        elif e[0] == "wood_clamp":
+            f.add(("wood<0", "wood in", "wood>1")[e[1] + 1])
+        elif e[0] == "wood2_clamp":
+            f.add("sine<0" if e[1] else "sine>=0")
+        elif e[0] == "clr_clamp":
+            f |= {("clr<0", "clr in", "clr>1")[v + 1] for v in e[1]}
+        elif e[0] == "stone":
+            f.add("mortar" if e[1] == 0 else "brick %d" % e[1])
+        elif e[0] in ("lit", "blocked"):
+            f.add(e[0])
+    return f
+
+
 # hand-placed photons of photon_irradiance_k5: offsets (dx, dy, dz) from the KAT pixel's hit point,
 # distinct distances (5 within the neighbourhood, 2 more within max_dist 0.5, 2 beyond it)
 PHOTON_OFFSETS = [(0.05, 0.0, 0.02), (-0.11, 0.0, 0.07), (0.13, 0.0, -0.09), (-0.04, 0.0, -0.17), (0.21, 0.0, 0.12),
@@ -1063,6 +1559,7 @@ def q1_q4_facts(sc, row, col):
 
 def main():
     out = {"about": __doc__.split("\n\n")[0], "seed": SEED, "W": 300, "H": 300, "kats": []}
+    taken = {}
     for name, cli, row, col, what in KATS:
         kat = {"name": name, "cli": cli, "row": row, "col": col, "what": what}
         if name.startswith("photon"):
@@ -1072,6 +1569,9 @@ def main():
         c = sc.pixel(row, col)
         path = [list(e) for e in TRACE]
         check_path(name, path, sc)
+        if cli[4:-4] in TEX_KATS:
+            assert any(e[0] == "proc" for e in path), (name, "misses the textured sphere")
+            taken.setdefault(cli[4:-4], set()).update(tex_branches(path))
         if name.startswith("bvh"):
             kat["facts"] = q1_q4_facts(kat_scene(kat, 300, 300), row, col)
         for ch in c:  # the ARGB int is exact only away from a truncation step
@@ -1080,6 +1580,8 @@ def main():
         kat.update({"rgb": c, "argb": argb(c), "path": path})
         out["kats"].append(kat)
         print(f"{name:26s} {cli:18s} ({row},{col}) rgb {c} argb {argb(c) & 0xFFFFFFFF:08X}")
+    for kind, (_, need) in TEX_KATS.items():  # each scene's pixels together take every branch
+        assert need <= taken[kind], (kind, sorted(need - taken[kind]))
     out["trTrans_plain"] = TR_TRANS_PLAIN
     (HERE / "kats.json").write_text(json.dumps(out, indent=1) + "\n")
 

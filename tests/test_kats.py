@@ -4,7 +4,8 @@ shaders (calcSimpleTransClr, calcTransClr with a real Fresnel split), the spot f
 disk-light sampling; since round 5 C3's BVH path in miniature (a translated 12-triangle myBVH: the
 root's dropped element Q1, the double leaf transform Q4, a mirror ray starting inside the root box
 Q2, shadow rays from the ghost point), a bilinear image texel and a k = 5 photon irradiance over
-hand-placed photons -- at 300 x 300, 1 spp. The oracle (CPU) and the HIP path (-m gpu) must reproduce
+hand-placed photons; and one scene per procedural texture kind (noise, wood, wood2, marble, stone with each
+distance function), six pixels each, derived from the Java's texture handlers -- at 300 x 300, 1 spp. The oracle (CPU) and the HIP path (-m gpu) must reproduce
 each pixel: float32 RGB within 2e-6 of the derived double colour for the first five (host libm vs
 fdlibm trig: an ulp), 1e-6 for the round-5 ones, and the ARGB int exactly (the script keeps every
 channel 1e-9 away from a truncation step)."""
@@ -22,6 +23,9 @@ KATS = json.loads((GOLDEN / "kats.json").read_text())
 TOL = 2e-6
 TOL_R5 = 1e-6  # the round-5 KATs (BVH, texel, photon irradiance)
 R5 = {"bvh_q1_q2_q4_tile", "bvh_q4_ghost_blocked", "earth_bilinear_texel", "photon_irradiance_k5"}
+# the procedural-texture KATs with no libm call on their path beyond sqrt (float noise; the Euclidean altLinROI
+# stone) go with them; wood, wood2, marble (sin) and the Manhattan stone (log) keep TOL
+R5 |= {"%s_%d" % (k, i) for k in ("noise", "stone_euclid") for i in range(6)}
 
 
 def _make_kats():

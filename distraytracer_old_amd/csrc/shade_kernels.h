@@ -2,6 +2,7 @@
 // whole shading tree (trace_kernels.h trace_sample, the reference's reflectRay), and the camera rays of a
 // frame as data (rt_camera_rays / rt_camera_rays_device).
 #pragma once
+#include "camera_ray.h"
 #include "trace_kernels.h"
 
 namespace rt {
@@ -62,78 +63,17 @@ shade_kernel_idx(SceneD S, uint64_t seed, uint64_t firstKey, uint32_t sample, co
   shade_ray<F>(S, seed, firstKey, sample, rays, (int64_t)order[slot], rgb, status);
 }
 
-// The ray render_kernel shoots for sample s of pixel first + i of a whole-frame layout (ray index = pixel
-// key = row * W + col), into rays[i]: the kernel's camera code operation for operation (myScene.java
-// :1386-1462 FOV / DOF, :1562-1622 fisheye, :1690-1745 ortho). The direction is stored as the kernel hands
-// it to trace_sample (not normalised), tmax = +Inf. A fisheye sample outside the image circle, which the
-// render does not trace, gets d = 0: every query rejects it.
+// camera_ray (camera_ray.h) for sample s of pixel first + i of a whole-frame layout (ray index = pixel key), into
+// rays[i], tmax = +Inf: jittered when the frame has two samples or more. An untraced fisheye sample gets
+// d = 0: every query rejects it.
 __global__ void __launch_bounds__(256) camera_rays_kernel(SceneD S, ParamsD P, int s, int64_t first, int64_t count,
                                                           rt_ray* __restrict__ rays) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= count) return;
   const int64_t px = first + i;
   const int row = (int)(px / P.W), col = (int)(px % P.W);
-  const uint64_t pixel = (uint64_t)row * (uint64_t)P.W + (uint64_t)col;
-  const int n = P.spp;
-  const bool dof = S.dof && P.cam == 0;
-  const double rayY = (-1 * (row - P.H / 2.0));
-  const double rayX = col - P.W / 2.0;
-  bool traced = true;
-  V o = mk(0, 0, 0), d = mk(0, 0, 0);
-  if (P.cam == 1) {  // myFishEyeScene: draw (1 spp) / shootMultiRays
-    double xVal, yVal, rSq;
-    if (n == 1) {
-      yVal = (row + P.yStart) * P.fishMult;
-      const double ySq = yVal * yVal;
-      xVal = (col + P.xStart) * P.fishMult;
-      rSq = xVal * xVal + ySq;
-      traced = !(rSq > 1);
-    } else {
-      yVal = ((row + P.yStart) + rng(P.seed, pixel, (uint32_t)s, 0, SITE_AA_Y, 0, -.5, .5)) * P.fishMult;
-      xVal = ((col + P.xStart) + rng(P.seed, pixel, (uint32_t)s, 0, SITE_AA_X, 0, -.5, .5)) * P.fishMult;
-      rSq = yVal * yVal + xVal * xVal;
-      traced = rSq <= 1;
-    }
-    const double r = sqrt(rSq), theta = r * P.aperHalf, phi = atan2(-yVal, xVal), sTh = jf::sin(theta);
-    o = mk(0, 0, 0);
-    d = mk(sTh * jf::cos(phi), sTh * jf::sin(phi), -jf::cos(theta));
-  } else if (P.cam == 2) {  // myOrthoScene: draw / shootMultiRays
-    const double rayYOffset = P.H / 2.0, rayXOffset = P.W / 2.0;
-    double rx, ry;
-    if (n == 1) {
-      ry = P.orthPerRow * (-1 * (row - rayYOffset));
-      rx = P.orthPerCol * (col - rayXOffset);
-    } else {
-      const double yB = P.orthPerRow * ((-1 * (row - rayYOffset)) - .5), xB = P.orthPerCol * (col - rayXOffset - .5);
-      ry = yB + (P.orthPerRow * rng(P.seed, pixel, (uint32_t)s, 0, SITE_AA_Y, 0, -.5, .5));
-      rx = xB + (P.orthPerCol * rng(P.seed, pixel, (uint32_t)s, 0, SITE_AA_X, 0, -.5, .5));
-    }
-    o = mk(rx, ry, 0);
-    d = mk(0, 0, -1);
-  } else if (dof) {  // shootMultiDpthOfFldRays: the pixel's lens centre and focal point, then the lens sample
-    const V lc = nrmz(mk(rayX, rayY, P.viewZ));
-    const double I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    V ld = nrmz(nrmz(lc));
-    V fo = xpt(I, mk(0, 0, 0)), fd = xvec(I, ld);
-    V fN = mk(0, 0, 1);
-    double pr = dot(fN, fd);
-    double t = -(dot(fN, fo) + S.lensFocal) / pr;
-    const V fpt = mk(fd.x * t + fo.x, fd.y * t + fo.y, fd.z * t + fo.z);
-    double th = rng(P.seed, pixel, (uint32_t)s, 0, SITE_DOF_ANG, 0, 0, TWO_PI_F);
-    V tt = nrmz(rot_axis(mk(0, 1, 0), mk(0, 0, -1), th));
-    double mm = rng(P.seed, pixel, (uint32_t)s, 0, SITE_DOF_RAD, 0, 0, S.lensRadius);
-    tt = mk(tt.x * mm, tt.y * mm, tt.z * mm);
-    o = mk(tt.x + lc.x, tt.y + lc.y, tt.z + lc.z);
-    d = sub(fpt, o);
-  } else if (n == 1) {  // myFOVScene.draw's 1-spp path: no jitter
-    o = mk(0, 0, 0);
-    d = mk(rayX, rayY, P.viewZ);
-  } else {  // shootMultiRays: y jitter drawn before x
-    double ry = rayY + rng(P.seed, pixel, (uint32_t)s, 0, SITE_AA_Y, 0, -.5, .5);
-    double rx = rayX + rng(P.seed, pixel, (uint32_t)s, 0, SITE_AA_X, 0, -.5, .5);
-    o = mk(0, 0, 0);
-    d = mk(rx, ry, P.viewZ);
-  }
+  V o, d;
+  const bool traced = camera_ray<(uint32_t)FT_ALL>(S, P, row, col, s, P.spp != 1, o, d);
   if (!traced) d = mk(0, 0, 0);
   double* w = (double*)(rays + i);
   w[0] = o.x; w[1] = o.y; w[2] = o.z;

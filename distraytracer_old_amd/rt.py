@@ -64,7 +64,11 @@ EXPORTS = ["rt_abi_version", "rt_build_id", "rt_last_error", "rt_device_count", 
            # added to ABI 7: the coherence order of RT_TRACE_SORT
            "rt_trace_order", "rt_trace_order_device",
            # added to ABI 7: radiance queries (the shading tree on caller rays) and a frame's camera rays
-           "rt_shade_rays", "rt_shade_rays_device", "rt_camera_rays", "rt_camera_rays_device"]
+           "rt_shade_rays", "rt_shade_rays_device", "rt_camera_rays", "rt_camera_rays_device",
+           # added to ABI 7: progressive sample accumulation (a frame that converges in place)
+           "rt_accum_create", "rt_accum_add", "rt_accum_samples", "rt_accum_resolve", "rt_accum_resolve_device",
+           "rt_accum_error", "rt_accum_error_device", "rt_accum_state", "rt_accum_restore", "rt_accum_reset",
+           "rt_accum_destroy"]
 
 _lib = None
 
@@ -185,6 +189,20 @@ def lib():
             L.rt_shade_rays_device.argtypes = [vp, vp, vp, i64, vp, vp, vp]
             L.rt_camera_rays.argtypes = [vp, vp, ctypes.c_int, vp]
             L.rt_camera_rays_device.argtypes = [vp, vp, ctypes.c_int, vp, vp]
+        if hasattr(L, "rt_accum_create"):  # added to ABI 7
+            vp, i64 = ctypes.c_void_p, ctypes.c_int64
+            L.rt_accum_create.argtypes = [vp, vp, ctypes.c_uint32, vp]
+            L.rt_accum_add.argtypes = [vp, ctypes.c_int, vp]
+            L.rt_accum_samples.argtypes = [vp, vp]
+            L.rt_accum_resolve.argtypes = [vp, vp, vp]
+            L.rt_accum_resolve_device.argtypes = [vp, vp, vp, vp]
+            L.rt_accum_error.argtypes = [vp, vp]
+            L.rt_accum_error_device.argtypes = [vp, vp, vp]
+            L.rt_accum_state.argtypes = [vp, vp, vp, vp]
+            L.rt_accum_restore.argtypes = [vp, i64, vp, vp]
+            L.rt_accum_reset.argtypes = [vp]
+            L.rt_accum_destroy.argtypes = [vp]
+            L.rt_accum_destroy.restype = None
         _lib = L
     return _lib
 
@@ -547,6 +565,7 @@ RENDER_SHCOMPACT = 8  # RT_RENDER_SHCOMPACT: a wave's shadow rays traced compact
 RENDER_NOWAVECULL = 16  # RT_RENDER_NOWAVECULL: no wave-level shadow candidate test (same image)
 RENDER_WAVEFRONT = 32  # RT_RENDER_WAVEFRONT: level-synchronous shading (same image)
 RENDER_PIXEL_WAVES = 64  # RT_RENDER_PIXEL_WAVES: one pixel per wave (same image)
+ACCUM_MOMENTS = 1  # RT_ACCUM_MOMENTS: the accumulator also keeps the per-channel sums of squares (error map)
 
 
 TRACE_ANY = 1  # RT_TRACE_ANY: occlusion (calcShadow) instead of the closest hit
@@ -834,6 +853,12 @@ class Scene:
         _check(lib().rt_camera_rays_device(self._h, ctypes.byref(p), sample, ctypes.c_void_p(rays_ptr or None),
                                            ctypes.c_void_p(stream or None)), "rt_camera_rays_device")
 
+    def accumulator(self, W, H, seed=0x5EED0001, flags=0, moments=False) -> "Accumulator":
+        """A W x H frame that converges in place (rt_accum_create): samples are added in chunks and the frame
+        so far resolved between them. flags: RENDER_GENERIC / RENDER_NOCULL; moments=True also keeps the sums
+        of squares the error map needs."""
+        return Accumulator(self, W, H, seed, flags, moments)
+
     def render_pixels_device(self, p: RenderParams, pixels: np.ndarray, rgb_ptr: int, argb_ptr: int, stream: int = 0):
         """Asynchronous one-sample-per-wave render of the listed pixels (host int32 list) into whole-frame buffers."""
         t = np.ascontiguousarray(pixels, dtype=np.int32)
@@ -858,6 +883,90 @@ class Scene:
     def close(self):
         if self._h:
             lib().rt_scene_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class Accumulator:
+    """Progressive sample accumulation on one scene (rt_accum*): after add(n) calls that total N >= 2 samples,
+    resolve() is Scene.render(spp=N) bit for bit, however the samples were cut into chunks. Holds a reference
+    to its scene (an accumulator must be closed before its scene)."""
+
+    def __init__(self, scene: Scene, W, H, seed=0x5EED0001, flags=0, moments=False):
+        self._h = None
+        self.scene, self.W, self.H, self.moments = scene, W, H, bool(moments)
+        p = params(W, H, 0, seed, flags=flags)
+        h = ctypes.c_void_p()
+        _check(lib().rt_accum_create(scene._h, ctypes.byref(p), ACCUM_MOMENTS if moments else 0, ctypes.byref(h)),
+               "rt_accum_create")
+        self._h = h
+
+    def add(self, count: int, stream: int = 0):
+        """Shade the next `count` samples of every pixel; asynchronous on `stream` (0: the scene's own)."""
+        _check(lib().rt_accum_add(self._h, count, ctypes.c_void_p(stream or None)), "rt_accum_add")
+
+    @property
+    def samples(self) -> int:
+        n = ctypes.c_int64(0)
+        _check(lib().rt_accum_samples(self._h, ctypes.byref(n)), "rt_accum_samples")
+        return n.value
+
+    def resolve(self):
+        """The frame of the samples so far -> (rgb float32 [H, W, 3], argb int32 [H, W]), as Scene.render."""
+        rgb = np.zeros((self.H, self.W, 3), dtype=np.float32)
+        argb = np.zeros((self.H, self.W), dtype=np.int32)
+        _check(lib().rt_accum_resolve(self._h, rgb.ctypes.data, argb.ctypes.data), "rt_accum_resolve")
+        return rgb, argb
+
+    def resolve_device(self, rgb_ptr: int, argb_ptr: int, stream: int = 0):
+        """resolve() into device buffers (either may be 0) on a HIP stream; the caller orders it against add."""
+        _check(lib().rt_accum_resolve_device(self._h, ctypes.c_void_p(rgb_ptr or None), ctypes.c_void_p(argb_ptr or None),
+                                             ctypes.c_void_p(stream or None)), "rt_accum_resolve_device")
+
+    def error(self) -> np.ndarray:
+        """The standard error of every pixel's mean, the largest of its channels -> float32 [H, W] (moments only)."""
+        err = np.zeros((self.H, self.W), dtype=np.float32)
+        _check(lib().rt_accum_error(self._h, err.ctypes.data), "rt_accum_error")
+        return err
+
+    def error_device(self, err_ptr: int, stream: int = 0):
+        _check(lib().rt_accum_error_device(self._h, ctypes.c_void_p(err_ptr or None), ctypes.c_void_p(stream or None)),
+               "rt_accum_error_device")
+
+    def state(self):
+        """The checkpoint: (samples, sum float64 [H, W, 3], sq float64 [H, W, 3] or None without moments)."""
+        n = ctypes.c_int64(0)
+        s = np.zeros((self.H, self.W, 3), dtype=np.float64)
+        q = np.zeros((self.H, self.W, 3), dtype=np.float64) if self.moments else None
+        _check(lib().rt_accum_state(self._h, ctypes.byref(n), s.ctypes.data, q.ctypes.data if self.moments else None),
+               "rt_accum_state")
+        return n.value, s, q
+
+    def restore(self, samples: int, sum, sq=None):
+        s = np.ascontiguousarray(sum, dtype=np.float64)
+        q = None if sq is None else np.ascontiguousarray(sq, dtype=np.float64)
+        if s.size != 3 * self.W * self.H or (q is not None and q.size != s.size):
+            raise ValueError("restore: sum and sq are float64 [H, W, 3]")
+        _check(lib().rt_accum_restore(self._h, samples, s.ctypes.data, None if q is None else q.ctypes.data),
+               "rt_accum_restore")
+
+    def reset(self):
+        _check(lib().rt_accum_reset(self._h), "rt_accum_reset")
+
+    def close(self):
+        if self._h:
+            lib().rt_accum_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -598,6 +598,68 @@ int rt_shade_rays_device(rt_scene* scene, const rt_shade_params* p, const rt_ray
 int rt_camera_rays(rt_scene* scene, const rt_render_params* p, int sample, rt_ray* rays);
 int rt_camera_rays_device(rt_scene* scene, const rt_render_params* p, int sample, rt_ray* d_rays, void* hip_stream);
 
+/* ---- Progressive sample accumulation (added to ABI 7; probe the eleven entries with dlsym) ------------
+   A frame that converges in place. An accumulator keeps, on its scene's device, the per-pixel and
+   per-channel sum of the samples shaded so far; the host adds samples in chunks of any size, and between
+   chunks resolves the frame so far, asks for its error map, checkpoints it or goes on.
+
+   rt_accum_create: p gives width, height, seed and flags; p->spp is ignored. Only RT_RENDER_GENERIC and
+   RT_RENDER_NOCULL are accepted in p->flags (any other bit is RT_E_INVALID, RT_RENDER_SHCOMPACT,
+   RT_RENDER_WAVEFRONT and RT_RENDER_PIXEL_WAVES included), only RT_ACCUM_MOMENTS in accum_flags. p's rows
+   must be the whole image (as for rt_render_pixels_device). Allocates double sum[3 * width * height],
+   zeroed, and with RT_ACCUM_MOMENTS a zeroed double sq[3 * width * height], row-major by pixel, r g b. A
+   scene that uses a photon map gets it built with p->seed, as by every render entry. An accumulator must
+   be destroyed before its scene.
+
+   rt_accum_add: shades samples [done, done + count) of every pixel, then done += count. count >= 1 and
+   done + count < 2^31. Asynchronous on hip_stream (NULL: the scene's own stream); it counts as the scene's
+   one in-flight render.
+
+   Sample s of a pixel is the ray a render of at least two samples shoots for sample s of that pixel (the
+   jittered field-of-view, fisheye or orthographic ray, or the depth-of-field ray as it is) -- the ray
+   rt_camera_rays emits for sample = s with spp >= 2 -- shaded under the key {seed, pixel = row * width +
+   col, s, node 1, camera-ray time site}. Neither depends on how many samples a frame has.
+
+   The sums: per pixel and channel sum = sum + c_s over the traced samples in increasing s, each step one
+   IEEE addition, starting from +0.0. A fisheye sample outside the image circle adds nothing but counts in
+   done (the render divides by spp). With RT_ACCUM_MOMENTS also sq = sq + (c_s * c_s), the product rounded
+   first and then added, never fused. Chunk invariance: add(a); add(b) leaves the same bytes in sum and sq
+   as add(a + b).
+
+   rt_accum_resolve / rt_accum_resolve_device: the frame of the n = done >= 1 samples so far (RT_E_INVALID
+   at n == 0): c = min(1, sum / n) per channel (the IEEE division), rgb = (float)c and argb the render's
+   packing. For n >= 2 that is rt_render(spp = n) with the same seed, bit for bit; for n == 1 it is in a
+   scene with a lens (elsewhere a 1-spp render shoots the un-jittered ray). Either output may be NULL.
+
+   rt_accum_error / rt_accum_error_device: needs RT_ACCUM_MOMENTS and n >= 2. err[width * height], per
+   pixel the largest over the three channels of, in fp64 and in exactly this order,
+       m = sum / n;  v = sq / n - m * m;  v = v < 0 ? 0 : v;  e = sqrt((v * n / (n - 1)) / n)
+   as a float: the standard error of the pixel's mean. A host stops when its maximum is small enough.
+
+   rt_accum_state copies out done and the raw sums (any output may be NULL; sq only from an accumulator
+   with moments), rt_accum_restore sets them (0 <= samples < 2^31; sq is refused unless the accumulator
+   keeps moments and required when it does): checkpoint and resume. rt_accum_reset zeroes the sums and
+   done. rt_accum_samples reads done.
+
+   Synchronisation: the accumulator remembers the stream of its last add. The host-buffer entries
+   (rt_accum_resolve, rt_accum_error, rt_accum_state, rt_accum_restore, rt_accum_reset) synchronise that
+   stream first and block. The _device entries run on the stream they are given; ordering them against
+   add is the caller's job. Bad arguments are RT_E_INVALID with a message that starts with the entry's
+   name, before the scene is touched; every entry restores the caller's current device. */
+typedef struct rt_accum rt_accum;
+#define RT_ACCUM_MOMENTS 1u /* also keep the per-channel sum of squares */
+int rt_accum_create(rt_scene* scene, const rt_render_params* p, uint32_t accum_flags, rt_accum** out);
+int rt_accum_add(rt_accum* a, int count, void* hip_stream);
+int rt_accum_samples(const rt_accum* a, int64_t* samples);
+int rt_accum_resolve(rt_accum* a, float* rgb, int32_t* argb);
+int rt_accum_resolve_device(rt_accum* a, float* d_rgb, int32_t* d_argb, void* hip_stream);
+int rt_accum_error(rt_accum* a, float* err);
+int rt_accum_error_device(rt_accum* a, float* d_err, void* hip_stream);
+int rt_accum_state(rt_accum* a, int64_t* samples, double* sum, double* sq);
+int rt_accum_restore(rt_accum* a, int64_t samples, const double* sum, const double* sq);
+int rt_accum_reset(rt_accum* a);
+void rt_accum_destroy(rt_accum* a);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,11 @@
 // calls myScene.draw() and saves rndrdImg as PNG (myScene.java:1185-1196).
 //
 //   rtrender <scene_dir> <file.cli> [-w W] [-h H] [-spp N] [-seed S] [-device D] [-o out.png]
-//            [-rgb out.f32] [-tex name=path.ppm]... [-time ITERS] [-nodir]
+//            [-rgb out.f32] [-tex name=path.ppm]... [-time ITERS] [-nodir] [-budget MS]
+//
+// -budget MS: the best frame MS milliseconds give, in place of -spp's fixed count -- samples are accumulated
+// (rt_accum_*) in chunks of 2, 2, 4, 8, ... doubling up to 64 until the wall time since the first chunk was
+// issued exceeds MS; prints "samples N" and writes the frame of those N samples.
 //
 // Without -o the image goes where myScene.saveFile puts it (myScene.java:1185-1196): the
 // `write` name (rt_scene_save_name) inside the folder "pics.<yyyy.MM.dd.hh.mm>" the scene
@@ -18,6 +22,7 @@
 
 #include <sys/stat.h>
 
+#include <chrono>
 #include <cstdio>
 #include <ctime>
 #include <cstdlib>
@@ -86,12 +91,13 @@ static bool write_png(const std::string& path, int w, int h, const int32_t* argb
 int main(int argc, char** argv) {
   if (argc < 3) {
     std::fprintf(stderr, "usage: %s <scene_dir> <file.cli> [-w W] [-h H] [-spp N] [-seed S] [-device D] "
-                         "[-o out.png] [-rgb out.f32] [-tex name=path.ppm]... [-time ITERS] [-nodir]\n", argv[0]);
+                         "[-o out.png] [-rgb out.f32] [-tex name=path.ppm]... [-time ITERS] [-nodir] [-budget MS]\n", argv[0]);
     return 2;
   }
   std::string dir = argv[1], cli = argv[2], out, rgbOut;
   bool inDir = true;
   int W = 300, H = 300, spp = 0, device = 0, timeIters = 0;  // DistRayTracer.java:15-16 default size
+  double budgetMs = -1;  // >= 0: accumulate for that long instead of rendering spp samples
   uint64_t seed = 0x5EED0001ull;
   std::vector<std::string> texNames, texPaths;
   for (int i = 3; i < argc; ++i) {
@@ -109,6 +115,7 @@ int main(int argc, char** argv) {
     else if (a == "-rgb") rgbOut = next();
     else if (a == "-time") timeIters = std::atoi(next().c_str());
     else if (a == "-nodir") inDir = false;
+    else if (a == "-budget") budgetMs = std::atof(next().c_str());
     else if (a == "-tex") {
       std::string t = next();
       size_t eq = t.find('=');
@@ -149,8 +156,25 @@ int main(int argc, char** argv) {
   p.width = W; p.height = H; p.spp = spp; p.row0 = 0; p.row1 = H; p.row_step = 1; p.seed = seed;
   std::vector<float> rgb((size_t)W * H * 3);
   std::vector<int32_t> argb((size_t)W * H);
-  rc = rt_render(s, &p, rgb.data(), argb.data());
-  if (rc) { std::fprintf(stderr, "rt_render: %d %s\n", rc, rt_last_error()); rt_scene_destroy(s); return 1; }
+  if (budgetMs >= 0) {
+    rt_accum* acc = nullptr;
+    rc = rt_accum_create(s, &p, 0, &acc);
+    int64_t n = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int chunk = 2, first = 1; rc == 0; first = 0) {
+      rc = rt_accum_add(acc, chunk, nullptr);
+      if (rc == 0) rc = rt_accum_state(acc, &n, nullptr, nullptr);  // waits for the chunk
+      if (std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() > budgetMs) break;
+      if (!first && chunk < 64) chunk *= 2;  // 2, 2, 4, 8, ... 64, 64, ...
+    }
+    if (rc == 0) rc = rt_accum_resolve(acc, rgb.data(), argb.data());
+    rt_accum_destroy(acc);
+    if (rc) { std::fprintf(stderr, "rt_accum: %d %s\n", rc, rt_last_error()); rt_scene_destroy(s); return 1; }
+    std::printf("samples %lld\n", (long long)n);
+  } else {
+    rc = rt_render(s, &p, rgb.data(), argb.data());
+    if (rc) { std::fprintf(stderr, "rt_render: %d %s\n", rc, rt_last_error()); rt_scene_destroy(s); return 1; }
+  }
   if (timeIters > 0) {
     double ms = 0;
     rc = rt_time_render(s, &p, 1, timeIters, &ms);

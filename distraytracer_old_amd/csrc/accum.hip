@@ -13,6 +13,7 @@
 #define RT_MINREG_TU
 #include "rt_internal.h"
 #include "comm.h"
+#include "accum_state.h"
 #include "accum_kernels.h"
 
 using namespace rt;
@@ -24,27 +25,11 @@ using namespace rt;
       return set_error(RT_E_HIP, std::string(#expr " failed: ") + hipGetErrorString(e_)); \
   } while (0)
 
-// The argument checks read nothing but these fields, and read them before anything else is touched.
-struct rt_accum {
-  uint32_t flags;  // RT_ACCUM_*
-  int32_t W, H;
-  int64_t done;  // samples accumulated per pixel
-  rt_scene* scene;
-  rt_render_params rp;  // the frame: size, seed, flags (spp is set per add)
-  double* sum;          // device [3 * W * H]
-  double* sq;           // device [3 * W * H], RT_ACCUM_MOMENTS only
-  void* last;           // hipStream_t of the last add
-};
-
-// tests/test_accum_abi.py hands the entries a host-made accumulator with these two fields set: the refusals
-// it checks must need no device
-static_assert(__builtin_offsetof(rt_accum, flags) == 0 && __builtin_offsetof(rt_accum, done) == 16, "rt_accum's checked fields");
-
 namespace {
 
 constexpr uint32_t F_C4 = dv::FT_PRIM | dv::FT_TRANS | dv::FT_TEX | dv::FT_LIGHTX;
 constexpr uint32_t RENDER_FLAGS = RT_RENDER_GENERIC | RT_RENDER_NOCULL;
-constexpr uint32_t ACCUM_FLAGS = RT_ACCUM_MOMENTS;
+constexpr uint32_t ACCUM_FLAGS = RT_ACCUM_MOMENTS | RT_ACCUM_COUNTS;
 
 typedef void (*AccumFn)(SceneD, ParamsD, int, double*, double*);
 struct AccumVariant {
@@ -98,7 +83,14 @@ int zero_sums(rt_accum* a) {
   return RT_OK;
 }
 
+// per-pixel counts that differ from done (RT_ACCUM_COUNTS after a selective add): adaptive.hip's kernels
+bool mixed_counts(const rt_accum* a) { return (a->flags & RT_ACCUM_COUNTS) && a->mixed; }
+// what the resolve and error entries ask of the samples so far: an accumulator with RT_ACCUM_COUNTS has some
+// as soon as one add of any kind happened (a pixel without enough of them resolves black, errs +Inf)
+int64_t samples_floor(const rt_accum* a) { return (a->flags & RT_ACCUM_COUNTS) ? (a->bound >= 1 ? 2 : 0) : a->done; }
+
 int launch_resolve(rt_accum* a, float* d_rgb, int32_t* d_argb, hipStream_t st) {
+  if (mixed_counts(a)) return adaptive_resolve(a, d_rgb, d_argb, st);
   const int64_t n = pixels(a);
   hipLaunchKernelGGL(dv::resolve_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a->sum, n, a->done, d_rgb, d_argb);
   HIPCHK(hipGetLastError());
@@ -106,6 +98,7 @@ int launch_resolve(rt_accum* a, float* d_rgb, int32_t* d_argb, hipStream_t st) {
 }
 
 int launch_error(rt_accum* a, float* d_err, hipStream_t st) {
+  if (mixed_counts(a) || ((a->flags & RT_ACCUM_COUNTS) && a->done < 2)) return adaptive_error(a, d_err, st);  // +Inf below two
   const int64_t n = pixels(a);
   hipLaunchKernelGGL(dv::error_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a->sum, a->sq, n, a->done, d_err);
   HIPCHK(hipGetLastError());
@@ -115,7 +108,7 @@ int launch_error(rt_accum* a, float* d_err, hipStream_t st) {
 int check_resolve(const char* who, const rt_accum* a) {
   const std::string w(who);
   if (!a) return set_error(RT_E_INVALID, w + ": null accumulator");
-  if (a->done < 1) return set_error(RT_E_INVALID, w + ": no samples accumulated yet");
+  if (samples_floor(a) < 1) return set_error(RT_E_INVALID, w + ": no samples accumulated yet");
   return RT_OK;
 }
 
@@ -124,7 +117,7 @@ int check_error(const char* who, const rt_accum* a, const float* err) {
   if (!a) return set_error(RT_E_INVALID, w + ": null accumulator");
   if (!err) return set_error(RT_E_INVALID, w + ": null err");
   if (!(a->flags & RT_ACCUM_MOMENTS)) return set_error(RT_E_INVALID, w + ": the accumulator was created without RT_ACCUM_MOMENTS");
-  if (a->done < 2) return set_error(RT_E_INVALID, w + ": needs at least two accumulated samples");
+  if (samples_floor(a) < 2) return set_error(RT_E_INVALID, w + ": needs at least two accumulated samples");
   return RT_OK;
 }
 
@@ -157,6 +150,8 @@ int rt_accum_create(rt_scene* s, const rt_render_params* p, uint32_t accum_flags
   if (p->flags & ~RENDER_FLAGS) return set_error(RT_E_INVALID, w + ": only RT_RENDER_GENERIC and RT_RENDER_NOCULL are accepted in flags");
   if (accum_flags & ~ACCUM_FLAGS) return set_error(RT_E_INVALID, w + ": unknown accum_flags bits");
   if (p->width <= 0 || p->height <= 0) return set_error(RT_E_INVALID, w + ": bad image size");
+  if ((accum_flags & RT_ACCUM_COUNTS) && (int64_t)p->width * p->height > INT32_MAX)
+    return set_error(RT_E_INVALID, w + ": RT_ACCUM_COUNTS needs width * height < 2^31");
   {  // the whole image, by rt_render_pixels_device's rule, from the arguments alone
     const int row1 = p->row1 <= 0 ? p->height : p->row1;
     if (p->row0 != 0 || row1 != p->height || p->row_step > 1 || p->row_band > 1)
@@ -187,10 +182,12 @@ int rt_accum_create(rt_scene* s, const rt_render_params* p, uint32_t accum_flags
   a->last = s->stream;
   hipError_t e = hipMalloc(&a->sum, sums_bytes(a));
   if (e == hipSuccess && (accum_flags & RT_ACCUM_MOMENTS)) e = hipMalloc(&a->sq, sums_bytes(a));
+  if (e == hipSuccess && (accum_flags & RT_ACCUM_COUNTS) && adaptive_alloc(a) != RT_OK) e = hipErrorOutOfMemory;
   if (e != hipSuccess || zero_sums(a) != RT_OK) {
     const std::string msg = e != hipSuccess ? w + ": " + hipGetErrorString(e) : w + ": " + rt_last_error();
     (void)hipFree(a->sum);
     (void)hipFree(a->sq);
+    adaptive_free(a);
     delete a;
     return set_error(RT_E_HIP, msg);
   }
@@ -202,7 +199,8 @@ int rt_accum_add(rt_accum* a, int count, void* hip_stream) {
   const std::string w("rt_accum_add");
   if (!a) return set_error(RT_E_INVALID, w + ": null accumulator");
   if (count < 1) return set_error(RT_E_INVALID, w + ": count must be at least 1");
-  if (a->done + (int64_t)count >= ((int64_t)1 << 31)) return set_error(RT_E_INVALID, w + ": more than 2^31 - 1 samples per pixel");
+  if ((a->done > a->bound ? a->done : a->bound) + (int64_t)count >= ((int64_t)1 << 31))
+    return set_error(RT_E_INVALID, w + ": more than 2^31 - 1 samples per pixel");
   DeviceGuard dg;
   rt_scene* s = a->scene;
   rt_render_params q = a->rp;
@@ -213,6 +211,13 @@ int rt_accum_add(rt_accum* a, int count, void* hip_stream) {
   HIPCHK(hipSetDevice(s->device));
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (hipStream_t)s->stream;
   const SceneD sd = render_scene_view(s, a->rp.flags & RT_RENDER_NOCULL);
+  if (mixed_counts(a)) {  // samples [cnt[p], cnt[p] + count) of every pixel
+    if ((rc = adaptive_add_all(a, P, st)) != RT_OK) return rc;
+    a->done += count;
+    a->bound += count;
+    a->last = st;
+    return RT_OK;
+  }
   const AccumVariant& v = accum_variant(s, a->rp.flags);
   const int64_t tilesX = (P.W + P.tw - 1) / P.tw, tilesY = (P.H + P.th - 1) / P.th;
   if (tilesX * tilesY > INT32_MAX) return set_error(RT_E_INVALID, w + ": more than 2^31 - 1 tiles");
@@ -220,6 +225,7 @@ int rt_accum_add(rt_accum* a, int count, void* hip_stream) {
                      a->sum, a->sq);
   HIPCHK(hipGetLastError());
   a->done += count;
+  if (a->flags & RT_ACCUM_COUNTS) a->bound += count;
   a->last = st;
   return RT_OK;
 }
@@ -303,6 +309,7 @@ int rt_accum_restore(rt_accum* a, int64_t samples, const double* sum, const doub
   if (sq) HIPCHK(hipMemcpyAsync(a->sq, sq, sums_bytes(a), hipMemcpyHostToDevice, st));
   HIPCHK(hipStreamSynchronize(st));
   a->done = samples;
+  if (a->flags & RT_ACCUM_COUNTS) adaptive_uniform(a, samples);
   return RT_OK;
 }
 
@@ -313,6 +320,7 @@ int rt_accum_reset(rt_accum* a) {
   if (rc != RT_OK) return rc;
   if ((rc = zero_sums(a)) != RT_OK) return rc;
   a->done = 0;
+  if (a->flags & RT_ACCUM_COUNTS) adaptive_uniform(a, 0);
   return RT_OK;
 }
 
@@ -323,6 +331,7 @@ void rt_accum_destroy(rt_accum* a) {
     (void)hipStreamSynchronize((hipStream_t)a->last);
     (void)hipFree(a->sum);
     (void)hipFree(a->sq);
+    adaptive_free(a);
   }
   delete a;
 }

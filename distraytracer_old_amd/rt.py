@@ -68,7 +68,10 @@ EXPORTS = ["rt_abi_version", "rt_build_id", "rt_last_error", "rt_device_count", 
            # added to ABI 7: progressive sample accumulation (a frame that converges in place)
            "rt_accum_create", "rt_accum_add", "rt_accum_samples", "rt_accum_resolve", "rt_accum_resolve_device",
            "rt_accum_error", "rt_accum_error_device", "rt_accum_state", "rt_accum_restore", "rt_accum_reset",
-           "rt_accum_destroy"]
+           "rt_accum_destroy",
+           # added to ABI 7: adaptive sampling (per-pixel sample counts, selections, the selective add)
+           "rt_accum_select_error", "rt_accum_select_mask", "rt_accum_select_mask_device", "rt_accum_selection",
+           "rt_accum_add_selected", "rt_accum_counts", "rt_accum_counts_device", "rt_accum_restore_counts"]
 
 _lib = None
 
@@ -203,6 +206,15 @@ def lib():
             L.rt_accum_reset.argtypes = [vp]
             L.rt_accum_destroy.argtypes = [vp]
             L.rt_accum_destroy.restype = None
+        if hasattr(L, "rt_accum_add_selected"):  # added to ABI 7
+            L.rt_accum_select_error.argtypes = [vp, ctypes.c_float, ctypes.c_int, vp]
+            L.rt_accum_select_mask.argtypes = [vp, vp, vp]
+            L.rt_accum_select_mask_device.argtypes = [vp, vp, vp, vp]
+            L.rt_accum_selection.argtypes = [vp, vp]
+            L.rt_accum_add_selected.argtypes = [vp, ctypes.c_int, vp]
+            L.rt_accum_counts.argtypes = [vp, vp]
+            L.rt_accum_counts_device.argtypes = [vp, vp, vp]
+            L.rt_accum_restore_counts.argtypes = [vp, vp]
         _lib = L
     return _lib
 
@@ -566,6 +578,7 @@ RENDER_NOWAVECULL = 16  # RT_RENDER_NOWAVECULL: no wave-level shadow candidate t
 RENDER_WAVEFRONT = 32  # RT_RENDER_WAVEFRONT: level-synchronous shading (same image)
 RENDER_PIXEL_WAVES = 64  # RT_RENDER_PIXEL_WAVES: one pixel per wave (same image)
 ACCUM_MOMENTS = 1  # RT_ACCUM_MOMENTS: the accumulator also keeps the per-channel sums of squares (error map)
+ACCUM_COUNTS = 4  # RT_ACCUM_COUNTS: the accumulator also keeps a sample count per pixel (adaptive sampling)
 
 
 TRACE_ANY = 1  # RT_TRACE_ANY: occlusion (calcShadow) instead of the closest hit
@@ -853,11 +866,11 @@ class Scene:
         _check(lib().rt_camera_rays_device(self._h, ctypes.byref(p), sample, ctypes.c_void_p(rays_ptr or None),
                                            ctypes.c_void_p(stream or None)), "rt_camera_rays_device")
 
-    def accumulator(self, W, H, seed=0x5EED0001, flags=0, moments=False) -> "Accumulator":
+    def accumulator(self, W, H, seed=0x5EED0001, flags=0, moments=False, counts=False) -> "Accumulator":
         """A W x H frame that converges in place (rt_accum_create): samples are added in chunks and the frame
         so far resolved between them. flags: RENDER_GENERIC / RENDER_NOCULL; moments=True also keeps the sums
-        of squares the error map needs."""
-        return Accumulator(self, W, H, seed, flags, moments)
+        of squares the error map needs, counts=True a sample count per pixel (select_* / add_selected)."""
+        return Accumulator(self, W, H, seed, flags, moments, counts)
 
     def render_pixels_device(self, p: RenderParams, pixels: np.ndarray, rgb_ptr: int, argb_ptr: int, stream: int = 0):
         """Asynchronous one-sample-per-wave render of the listed pixels (host int32 list) into whole-frame buffers."""
@@ -903,13 +916,13 @@ class Accumulator:
     resolve() is Scene.render(spp=N) bit for bit, however the samples were cut into chunks. Holds a reference
     to its scene (an accumulator must be closed before its scene)."""
 
-    def __init__(self, scene: Scene, W, H, seed=0x5EED0001, flags=0, moments=False):
-        self._h = None
-        self.scene, self.W, self.H, self.moments = scene, W, H, bool(moments)
+    def __init__(self, scene: Scene, W, H, seed=0x5EED0001, flags=0, moments=False, counts=False):
+        self._h, self._nsel = None, 0
+        self.scene, self.W, self.H, self.moments, self.has_counts = scene, W, H, bool(moments), bool(counts)
         p = params(W, H, 0, seed, flags=flags)
         h = ctypes.c_void_p()
-        _check(lib().rt_accum_create(scene._h, ctypes.byref(p), ACCUM_MOMENTS if moments else 0, ctypes.byref(h)),
-               "rt_accum_create")
+        _check(lib().rt_accum_create(scene._h, ctypes.byref(p), (ACCUM_MOMENTS if moments else 0) | (ACCUM_COUNTS if counts else 0),
+                                     ctypes.byref(h)), "rt_accum_create")
         self._h = h
 
     def add(self, count: int, stream: int = 0):
@@ -963,6 +976,60 @@ class Accumulator:
 
     def reset(self):
         _check(lib().rt_accum_reset(self._h), "rt_accum_reset")
+
+    # ---- adaptive sampling (counts=True) ----
+    def select_error(self, threshold: float, max_samples: int) -> int:
+        """Select the pixels with fewer than max_samples samples whose error() exceeds threshold (or is NaN, or
+        that have fewer than two samples) -> how many (moments only). Blocks."""
+        n = ctypes.c_int64(0)
+        _check(lib().rt_accum_select_error(self._h, threshold, max_samples, ctypes.byref(n)), "rt_accum_select_error")
+        self._nsel = n.value
+        return n.value
+
+    def select_mask(self, mask) -> int:
+        """Select the pixels where mask [H, W] is nonzero -> how many. Blocks."""
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if m.size != self.W * self.H:
+            raise ValueError("select_mask: mask is [H, W]")
+        n = ctypes.c_int64(0)
+        _check(lib().rt_accum_select_mask(self._h, m.ctypes.data, ctypes.byref(n)), "rt_accum_select_mask")
+        self._nsel = n.value
+        return n.value
+
+    def select_mask_device(self, mask_ptr: int, stream: int = 0) -> int:
+        """select_mask from a device uint8 [H, W] mask on a HIP stream -> how many. Blocks."""
+        n = ctypes.c_int64(0)
+        _check(lib().rt_accum_select_mask_device(self._h, ctypes.c_void_p(mask_ptr or None), ctypes.c_void_p(stream or None),
+                                                 ctypes.byref(n)), "rt_accum_select_mask_device")
+        self._nsel = n.value
+        return n.value
+
+    def selection(self) -> np.ndarray:
+        """The current selection's pixel indices (row * W + col, int32), in its tile-major order."""
+        px = np.zeros(self.W * self.H, dtype=np.int32)
+        _check(lib().rt_accum_selection(self._h, px.ctypes.data), "rt_accum_selection")
+        return px[: self._nsel]
+
+    def add_selected(self, count: int, stream: int = 0):
+        """Shade the next `count` samples of every selected pixel; asynchronous on `stream` (0: the scene's own)."""
+        _check(lib().rt_accum_add_selected(self._h, count, ctypes.c_void_p(stream or None)), "rt_accum_add_selected")
+
+    def counts(self) -> np.ndarray:
+        """The samples each pixel has received -> int32 [H, W]."""
+        c = np.zeros((self.H, self.W), dtype=np.int32)
+        _check(lib().rt_accum_counts(self._h, c.ctypes.data), "rt_accum_counts")
+        return c
+
+    def counts_device(self, cnt_ptr: int, stream: int = 0):
+        _check(lib().rt_accum_counts_device(self._h, ctypes.c_void_p(cnt_ptr or None), ctypes.c_void_p(stream or None)),
+               "rt_accum_counts_device")
+
+    def restore_counts(self, cnt):
+        """After restore(): the per-pixel counts of a checkpoint (int32 [H, W])."""
+        c = np.ascontiguousarray(cnt, dtype=np.int32)
+        if c.size != self.W * self.H:
+            raise ValueError("restore_counts: cnt is int32 [H, W]")
+        _check(lib().rt_accum_restore_counts(self._h, c.ctypes.data), "rt_accum_restore_counts")
 
     def close(self):
         if self._h:

@@ -605,8 +605,8 @@ int rt_camera_rays_device(rt_scene* scene, const rt_render_params* p, int sample
 
    rt_accum_create: p gives width, height, seed and flags; p->spp is ignored. Only RT_RENDER_GENERIC and
    RT_RENDER_NOCULL are accepted in p->flags (any other bit is RT_E_INVALID, RT_RENDER_SHCOMPACT,
-   RT_RENDER_WAVEFRONT and RT_RENDER_PIXEL_WAVES included), only RT_ACCUM_MOMENTS in accum_flags. p's rows
-   must be the whole image (as for rt_render_pixels_device). Allocates double sum[3 * width * height],
+   RT_RENDER_WAVEFRONT and RT_RENDER_PIXEL_WAVES included), only RT_ACCUM_MOMENTS and RT_ACCUM_COUNTS
+   (adaptive sampling, below) in accum_flags. p's rows must be the whole image (as for rt_render_pixels_device). Allocates double sum[3 * width * height],
    zeroed, and with RT_ACCUM_MOMENTS a zeroed double sq[3 * width * height], row-major by pixel, r g b. A
    scene that uses a photon map gets it built with p->seed, as by every render entry. An accumulator must
    be destroyed before its scene.
@@ -659,6 +659,58 @@ int rt_accum_state(rt_accum* a, int64_t* samples, double* sum, double* sq);
 int rt_accum_restore(rt_accum* a, int64_t samples, const double* sum, const double* sq);
 int rt_accum_reset(rt_accum* a);
 void rt_accum_destroy(rt_accum* a);
+
+/* ---- Adaptive sampling (added to ABI 7; probe the eight entries with dlsym) -----------------------------
+   Samples only where the frame is still noisy. An accumulator created with RT_ACCUM_COUNTS also keeps
+   int32 cnt[width * height] on its device, zeroed at creation and by rt_accum_reset: the samples each pixel
+   has received. Wherever the contract above says done, read cnt[p] for such an accumulator:
+   rt_accum_add adds samples [cnt[p], cnt[p] + count) to every pixel; rt_accum_resolve* divides pixel p by
+   cnt[p], and a pixel with cnt[p] == 0 resolves to colour 0 and ARGB 0xFF000000; rt_accum_error* uses
+   n = cnt[p] in the same expression and gives +Inf where cnt[p] < 2. Their refusals at done == 0 and
+   done < 2 become "no add of any kind happened yet". rt_accum_samples keeps reporting the samples
+   rt_accum_add gave every pixel. It needs width * height < 2^31. A pixel that has received n >= 2 samples
+   holds exactly what rt_render(spp = n) gives that pixel, bit for bit, however the pixels were selected and
+   however the samples were cut into chunks. An accumulator created without the flag behaves as before in
+   every entry, and every entry below refuses it.
+
+   A selection is a list of pixel indices row * width + col on the device, in tile-major order: the 8 x 8
+   tiles row-major over the image, within a tile the 6-bit Morton order whose bit 0 is bit 0 of the column
+   (code = x0 | y0 << 1 | x1 << 2 | y1 << 3 | x2 << 4 | y2 << 5), pixels outside the image skipped. The order
+   never depends on scheduling. Consecutive runs of 4, 16 and 64 entries of a dense selection are image
+   neighbours, which keeps a wave's traversal coherent: select whole regions rather than scattered pixels
+   where there is a choice. A selection stays valid until the next select, rt_accum_reset,
+   rt_accum_restore or rt_accum_restore_counts. The select entries wait for the last add, block, and
+   return the number of selected pixels in *selected.
+     rt_accum_select_error (needs RT_ACCUM_MOMENTS, threshold >= 0, 1 <= max_samples < 2^31): pixel p is
+       selected iff cnt[p] < max_samples and (cnt[p] < 2 or e_p > threshold), e_p exactly the float
+       rt_accum_error returns for p; a NaN e_p selects.
+     rt_accum_select_mask: a host mask[width * height], nonzero = selected.
+     rt_accum_select_mask_device: the same from a device mask, on hip_stream (NULL: the accumulator's).
+     rt_accum_selection: the current list copied to pixels[selected] on the host.
+
+   rt_accum_add_selected: for every pixel p of the current selection shades samples [cnt[p], cnt[p] +
+   count), then cnt[p] += count; sums and squares by rt_accum_add's rules. Asynchronous on hip_stream
+   (NULL: the scene's own stream); it counts as the scene's one in-flight render. An empty selection is
+   RT_OK and launches nothing; no selection made is RT_E_INVALID. count >= 1, and count < 2^31 - max(cnt),
+   where the maximum is tracked on the host as the sum of the counts of every add of either kind (after
+   rt_accum_restore_counts: from the largest restored count). Chunk invariance: add_selected(a);
+   add_selected(b) leaves the same bytes in sum, sq and cnt as add_selected(a + b).
+
+   rt_accum_counts (host, waits for the last add) and rt_accum_counts_device (asynchronous on hip_stream)
+   copy cnt out. rt_accum_restore on such an accumulator sets every cnt[p] = samples;
+   rt_accum_restore_counts, called after it, then sets cnt per pixel (every entry in [0, 2^31)).
+
+   Bad arguments are RT_E_INVALID with a message that starts with the entry's name, before the scene is
+   touched; every entry restores the caller's current device. */
+#define RT_ACCUM_COUNTS 4u /* also keep a sample count per pixel (2u is not a flag) */
+int rt_accum_select_error(rt_accum* a, float threshold, int max_samples, int64_t* selected);
+int rt_accum_select_mask(rt_accum* a, const uint8_t* mask, int64_t* selected);
+int rt_accum_select_mask_device(rt_accum* a, const uint8_t* d_mask, void* hip_stream, int64_t* selected);
+int rt_accum_selection(rt_accum* a, int32_t* pixels);
+int rt_accum_add_selected(rt_accum* a, int count, void* hip_stream);
+int rt_accum_counts(rt_accum* a, int32_t* cnt);
+int rt_accum_counts_device(rt_accum* a, int32_t* d_cnt, void* hip_stream);
+int rt_accum_restore_counts(rt_accum* a, const int32_t* cnt);
 
 #ifdef __cplusplus
 }

@@ -3,11 +3,17 @@
 // calls myScene.draw() and saves rndrdImg as PNG (myScene.java:1185-1196).
 //
 //   rtrender <scene_dir> <file.cli> [-w W] [-h H] [-spp N] [-seed S] [-device D] [-o out.png]
-//            [-rgb out.f32] [-tex name=path.ppm]... [-time ITERS] [-nodir] [-budget MS]
+//            [-rgb out.f32] [-tex name=path.ppm]... [-time ITERS] [-nodir] [-budget MS] [-noise E [-max N]]
 //
 // -budget MS: the best frame MS milliseconds give, in place of -spp's fixed count -- samples are accumulated
 // (rt_accum_*) in chunks of 2, 2, 4, 8, ... doubling up to 64 until the wall time since the first chunk was
 // issued exceeds MS; prints "samples N" and writes the frame of those N samples.
+//
+// -noise E [-max N]: samples only where the frame is still noisy (rt_accum_select_error / rt_accum_add_selected).
+// Every pixel gets 4 samples; then, until no pixel is selected, the pixels whose standard error exceeds E and
+// that have fewer than N samples (default 1024) get 4, 8, 16, ... doubling up to 64 more, a chunk never taking
+// a pixel past N. Prints "pixels W*H samples TOTAL max MAXCOUNT" (the samples shaded in all and the largest
+// count of a pixel) and writes the resolved frame.
 //
 // Without -o the image goes where myScene.saveFile puts it (myScene.java:1185-1196): the
 // `write` name (rt_scene_save_name) inside the folder "pics.<yyyy.MM.dd.hh.mm>" the scene
@@ -91,13 +97,16 @@ static bool write_png(const std::string& path, int w, int h, const int32_t* argb
 int main(int argc, char** argv) {
   if (argc < 3) {
     std::fprintf(stderr, "usage: %s <scene_dir> <file.cli> [-w W] [-h H] [-spp N] [-seed S] [-device D] "
-                         "[-o out.png] [-rgb out.f32] [-tex name=path.ppm]... [-time ITERS] [-nodir] [-budget MS]\n", argv[0]);
+                         "[-o out.png] [-rgb out.f32] [-tex name=path.ppm]... [-time ITERS] [-nodir] [-budget MS] "
+                         "[-noise E [-max N]]\n", argv[0]);
     return 2;
   }
   std::string dir = argv[1], cli = argv[2], out, rgbOut;
   bool inDir = true;
   int W = 300, H = 300, spp = 0, device = 0, timeIters = 0;  // DistRayTracer.java:15-16 default size
   double budgetMs = -1;  // >= 0: accumulate for that long instead of rendering spp samples
+  double noise = -1;     // >= 0: sample adaptively down to that standard error
+  int maxSamples = 1024;
   uint64_t seed = 0x5EED0001ull;
   std::vector<std::string> texNames, texPaths;
   for (int i = 3; i < argc; ++i) {
@@ -116,6 +125,8 @@ int main(int argc, char** argv) {
     else if (a == "-time") timeIters = std::atoi(next().c_str());
     else if (a == "-nodir") inDir = false;
     else if (a == "-budget") budgetMs = std::atof(next().c_str());
+    else if (a == "-noise") noise = std::atof(next().c_str());
+    else if (a == "-max") maxSamples = std::atoi(next().c_str());
     else if (a == "-tex") {
       std::string t = next();
       size_t eq = t.find('=');
@@ -156,7 +167,30 @@ int main(int argc, char** argv) {
   p.width = W; p.height = H; p.spp = spp; p.row0 = 0; p.row1 = H; p.row_step = 1; p.seed = seed;
   std::vector<float> rgb((size_t)W * H * 3);
   std::vector<int32_t> argb((size_t)W * H);
-  if (budgetMs >= 0) {
+  if (noise >= 0) {
+    if (maxSamples < 1) { std::fprintf(stderr, "-max expects at least 1\n"); rt_scene_destroy(s); return 2; }
+    rt_accum* acc = nullptr;
+    rc = rt_accum_create(s, &p, RT_ACCUM_MOMENTS | RT_ACCUM_COUNTS, &acc);
+    int top = maxSamples < 4 ? maxSamples : 4;  // no pixel has more samples than this
+    if (rc == 0) rc = rt_accum_add(acc, top, nullptr);
+    for (int chunk = 4; rc == 0; chunk = chunk < 64 ? chunk * 2 : 64) {
+      int64_t picked = 0;
+      rc = rt_accum_select_error(acc, (float)noise, maxSamples, &picked);
+      const int c = chunk < maxSamples - top ? chunk : maxSamples - top;
+      if (rc || picked == 0 || c < 1) break;
+      rc = rt_accum_add_selected(acc, c, nullptr);
+      top += c;
+    }
+    std::vector<int32_t> cnt((size_t)W * H);
+    if (rc == 0) rc = rt_accum_counts(acc, cnt.data());
+    if (rc == 0) rc = rt_accum_resolve(acc, rgb.data(), argb.data());
+    rt_accum_destroy(acc);
+    if (rc) { std::fprintf(stderr, "rt_accum: %d %s\n", rc, rt_last_error()); rt_scene_destroy(s); return 1; }
+    long long total = 0;
+    int most = 0;
+    for (int32_t v : cnt) { total += v; most = v > most ? v : most; }
+    std::printf("pixels %lld samples %lld max %d\n", (long long)W * H, total, most);
+  } else if (budgetMs >= 0) {
     rt_accum* acc = nullptr;
     rc = rt_accum_create(s, &p, 0, &acc);
     int64_t n = 0;

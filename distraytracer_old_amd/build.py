@@ -28,14 +28,14 @@ LIB_PATH = LIB_DIR / "libdistraytracer.so"
 INFO_PATH = LIB_DIR / "libdistraytracer.buildinfo.json"
 PUBLIC_HEADER = PKG.parent / "include" / "distraytracer.h"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-SOURCES = ["trace.hip", "render_minreg.hip", "query.hip", "ray_sort.hip", "shade.hip", "accum.hip", "adaptive.hip", "photon_build.hip", "group.hip", "comm.hip", "cli_loader.cpp",
+SOURCES = ["trace.hip", "render_minreg.hip", "query.hip", "ray_sort.hip", "shade.hip", "accum.hip", "adaptive.hip", "denoise.hip", "photon_build.hip", "group.hip", "comm.hip", "cli_loader.cpp",
            "scene_build.cpp", "photon.cpp", "build_id.cpp"]
 OBJ_DIR = LIB_DIR / "obj"
 # per-source compiler flags: render_minreg.hip holds C3's and C5's render variants, which run
 # faster with the register-minimising scheduler (C4's variant, in trace.hip, runs slower with it)
 SOURCE_FLAGS = {"render_minreg.hip": ["-Xarch_device", "-mllvm=--amdgpu-sched-strategy=iterative-minreg",
                                       "-Xarch_device", "-mllvm=--amdgpu-use-amdgpu-trackers=1"]}
-HEADERS = ["rt_types.h", "rt_internal.h", "comm.h", "host_math.h", "trace_device.h", "trace_kernels.h", "query_kernels.h", "shade_kernels.h", "accum_kernels.h", "accum_state.h", "adaptive_kernels.h", "camera_ray.h",
+HEADERS = ["rt_types.h", "rt_internal.h", "comm.h", "host_math.h", "trace_device.h", "trace_kernels.h", "query_kernels.h", "shade_kernels.h", "accum_kernels.h", "accum_state.h", "adaptive_kernels.h", "denoise_kernels.h", "camera_ray.h",
            "wavefront.h", "qdiv.h", "jfdlibm.h"]
 # -ffp-contract=off: keep the reference's (Java) unfused double arithmetic so discrete
 # decisions (hits, shadows, TIR) match the oracle; no fast-math (IEEE Inf/NaN needed).

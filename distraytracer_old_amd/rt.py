@@ -71,7 +71,10 @@ EXPORTS = ["rt_abi_version", "rt_build_id", "rt_last_error", "rt_device_count", 
            "rt_accum_destroy",
            # added to ABI 7: adaptive sampling (per-pixel sample counts, selections, the selective add)
            "rt_accum_select_error", "rt_accum_select_mask", "rt_accum_select_mask_device", "rt_accum_selection",
-           "rt_accum_add_selected", "rt_accum_counts", "rt_accum_counts_device", "rt_accum_restore_counts"]
+           "rt_accum_add_selected", "rt_accum_counts", "rt_accum_counts_device", "rt_accum_restore_counts",
+           # added to ABI 7: the variance-guided a-trous denoiser of an accumulated frame
+           "rt_denoise_defaults", "rt_denoise_create", "rt_denoise_guides", "rt_denoise_run", "rt_denoise_run_device",
+           "rt_denoise_planes", "rt_denoise_destroy"]
 
 _lib = None
 
@@ -215,6 +218,15 @@ def lib():
             L.rt_accum_counts.argtypes = [vp, vp]
             L.rt_accum_counts_device.argtypes = [vp, vp, vp]
             L.rt_accum_restore_counts.argtypes = [vp, vp]
+        if hasattr(L, "rt_denoise_run"):  # added to ABI 7
+            L.rt_denoise_defaults.argtypes = [vp]
+            L.rt_denoise_create.argtypes = [vp, vp]
+            L.rt_denoise_guides.argtypes = [vp, vp, vp, vp, vp]
+            L.rt_denoise_run.argtypes = [vp, vp, vp, vp]
+            L.rt_denoise_run_device.argtypes = [vp, vp, vp, vp, vp]
+            L.rt_denoise_planes.argtypes = [vp, vp, vp]
+            L.rt_denoise_destroy.argtypes = [vp]
+            L.rt_denoise_destroy.restype = None
         _lib = L
     return _lib
 
@@ -1031,9 +1043,90 @@ class Accumulator:
             raise ValueError("restore_counts: cnt is int32 [H, W]")
         _check(lib().rt_accum_restore_counts(self._h, c.ctypes.data), "rt_accum_restore_counts")
 
+    def denoiser(self) -> "Denoiser":
+        """The variance-guided a-trous denoiser of this frame (rt_denoise_create; moments only): builds the guides
+        of the frame's centre rays once. Close it before the accumulator."""
+        return Denoiser(self)
+
     def close(self):
         if self._h:
             lib().rt_accum_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class DenoiseParams(ctypes.Structure):
+    """rt_denoise_params; DenoiseParams.defaults() is rt_denoise_defaults, keyword arguments override fields."""
+    _fields_ = [("levels", ctypes.c_int32), ("normal_log2", ctypes.c_int32), ("sigma_l", ctypes.c_double),
+                ("sigma_z", ctypes.c_double)]
+
+    @classmethod
+    def defaults(cls, **over) -> "DenoiseParams":
+        p = cls()
+        _check(lib().rt_denoise_defaults(ctypes.byref(p)), "rt_denoise_defaults")
+        for k, v in over.items():
+            if k not in ("levels", "normal_log2", "sigma_l", "sigma_z"):
+                raise TypeError(f"unknown denoise parameter {k}")
+            setattr(p, k, v)
+        return p
+
+
+class Denoiser:
+    """The denoise step of an Accumulator's frame (rt_denoise_*): an edge-avoiding a-trous filter whose colour
+    edge-stop is scaled by the per-pixel variance of the mean. Holds a reference to its accumulator (a denoiser
+    must be closed before it). Parameters are DenoiseParams fields given as keywords over the defaults."""
+
+    def __init__(self, accum: Accumulator):
+        self._h = None
+        self.accum, self.W, self.H = accum, accum.W, accum.H
+        h = ctypes.c_void_p()
+        _check(lib().rt_denoise_create(accum._h, ctypes.byref(h)), "rt_denoise_create")
+        self._h = h
+
+    def guides(self) -> dict:
+        """The guides of the frame's centre rays: normal float32 [H, W, 3], pos float32 [H, W, 3], depth float32
+        [H, W], material int32 [H, W] (-1 and zeros where the ray missed or was rejected)."""
+        g = {"normal": np.zeros((self.H, self.W, 3), dtype=np.float32), "pos": np.zeros((self.H, self.W, 3), dtype=np.float32),
+             "depth": np.zeros((self.H, self.W), dtype=np.float32), "material": np.zeros((self.H, self.W), dtype=np.int32)}
+        _check(lib().rt_denoise_guides(self._h, g["normal"].ctypes.data, g["pos"].ctypes.data, g["depth"].ctypes.data,
+                                       g["material"].ctypes.data), "rt_denoise_guides")
+        return g
+
+    def run(self, **params):
+        """The denoised frame of the samples so far -> (rgb float32 [H, W, 3], argb int32 [H, W]). Blocks."""
+        p = DenoiseParams.defaults(**params)
+        rgb = np.zeros((self.H, self.W, 3), dtype=np.float32)
+        argb = np.zeros((self.H, self.W), dtype=np.int32)
+        _check(lib().rt_denoise_run(self._h, ctypes.byref(p), rgb.ctypes.data, argb.ctypes.data), "rt_denoise_run")
+        return rgb, argb
+
+    def run_device(self, rgb_ptr: int, argb_ptr: int, stream: int = 0, **params):
+        """run() into device buffers (either may be 0) on a HIP stream; the caller orders it against add."""
+        p = DenoiseParams.defaults(**params)
+        _check(lib().rt_denoise_run_device(self._h, ctypes.byref(p), ctypes.c_void_p(rgb_ptr or None), ctypes.c_void_p(argb_ptr or None),
+                                           ctypes.c_void_p(stream or None)), "rt_denoise_run_device")
+
+    def planes(self):
+        """The last run's final fp64 planes -> (colour float64 [H, W, 3], variance of the mean float64 [H, W])."""
+        c = np.zeros((self.H, self.W, 3), dtype=np.float64)
+        v = np.zeros((self.H, self.W), dtype=np.float64)
+        _check(lib().rt_denoise_planes(self._h, c.ctypes.data, v.ctypes.data), "rt_denoise_planes")
+        return c, v
+
+    def close(self):
+        if self._h:
+            lib().rt_denoise_destroy(self._h)
             self._h = None
 
     def __del__(self):

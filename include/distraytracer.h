@@ -712,6 +712,93 @@ int rt_accum_counts(rt_accum* a, int32_t* cnt);
 int rt_accum_counts_device(rt_accum* a, int32_t* d_cnt, void* hip_stream);
 int rt_accum_restore_counts(rt_accum* a, const int32_t* cnt);
 
+/* ---- Denoising an accumulated frame (added to ABI 7; probe the seven entries with dlsym) -----------------
+   An edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over an accumulator's mean, whose colour
+   edge-stop is scaled by the per-pixel variance of the mean (the spatial half of SVGF, Schied et al. 2017):
+   narrow where the estimate is already certain (texture detail, converged pixels), wide where it is noisy.
+   The filter uses no transcendental function; every step below is one IEEE fp64 operation in the order
+   written (sqrt and the division included), so a restatement that keeps the order gives the same bytes.
+
+   rt_denoise_create needs an accumulator with RT_ACCUM_MOMENTS. It waits for the accumulator's last add,
+   builds the guides (below), blocks until they are built, and allocates per pixel 32 bytes of guides, two
+   32-byte plane records and 16 bytes of frame staging on the accumulator's device. A denoiser must be
+   destroyed before its accumulator. rt_denoise_defaults fills the parameters DESIGN.md section 17 arrives at.
+
+   Guides. The rays are those rt_camera_rays_device emits for spp = 1, sample = 0 of the accumulator's frame:
+   the un-jittered ray through the pixel's centre, or in a scene with a lens the one lens ray of sample 0
+   (guides under depth of field are single-sample: they are as blurred as one sample is). They are traced by
+   rt_trace_rays_device: closest hit, the default packet traversal, the accumulator's RT_RENDER_GENERIC /
+   RT_RENDER_NOCULL as RT_TRACE_GENERIC / RT_TRACE_NOCULL, seed = the accumulator's seed, first_key = 0. Per
+   pixel, from its rt_hit h and its ray's origin o:
+       normal = (float)h.normal, material = h.material, pos = (float)h.pos,
+       depth = (float)sqrt(dx * dx + dy * dy + dz * dz), (dx, dy, dz) = h.pos - o, summed left to right.
+   A miss or a rejected ray (a fisheye pixel outside the image circle) has material -1 and +0 everywhere else.
+   The discrete guide is the material, not the primitive: a mesh is many primitives of one surface. The build
+   counts as the scene's one in-flight render. rt_denoise_guides copies them out: normal[3 * width * height],
+   pos[3 * width * height], depth[width * height], material[width * height], row-major; any may be NULL.
+
+   Init. n_p is the samples of pixel p: done, or cnt[p] of an accumulator with RT_ACCUM_COUNTS. Guides are
+   widened from float to double exactly.
+       n_p >= 1:  c_k = min(1, sum_k / n_p) per channel k (rt_accum_resolve's double).
+       n_p >= 2:  v_p = the largest over the channels of ((v * n) / (n - 1)) / n, with m = sum_k / n,
+                  v = sq_k / n - m * m, v = v < 0 ? 0 : v (rt_accum_error's expression before its sqrt, in
+                  its order: the variance of the mean).
+       n_p == 1:  v_p = 1.
+       n_p == 0:  c = 0, v_p = 1, and the pixel is out of the filter: no level changes its record, no other
+                  pixel takes it as a tap, and its output is colour 0 and ARGB 0xFF000000.
+
+   Level i = 0 .. levels - 1, tap stride s = 2^i, reads the planes (c, v) and gives (c', v'). For a pixel p
+   at (x, y) that is in the filter, with eps = 1e-10:
+       g_p = the sum, row-major over (dy, dx) in {-1, 0, 1}^2 and starting from +0.0, of
+             (b[dy] * b[dx]) * v at (clamp(x + dx, 0, width - 1), clamp(y + dy, 0, height - 1)),
+             b = [1/4, 1/2, 1/4] (the read takes v as it stands, also of a pixel out of the filter)
+       d_p = sigma_l * sqrt(g_p) + eps,   z_p = sigma_z * depth_p + eps
+       S = C_k = V = +0.0; then the taps (dy, dx) in {-2 .. 2}^2, row-major, h = [1/16, 1/4, 3/8, 1/4, 1/16],
+       q = (x + dx * s, y + dy * s). A tap is skipped when q is outside the image, when n_q == 0, or when it is
+       not the centre and material_q != material_p. The centre tap has w = 1. For every other tap
+           material_p == -1 (both are misses):  w_n = 1, u_z = 1
+           otherwise:  t = (nx_p * nx_q + ny_p * ny_q) + nz_p * nz_q;  w_n = t > 0 ? t : 0, then squared
+                       (w_n = w_n * w_n) normal_log2 times;
+                       e = pos_q - pos_p per component;  r = |(nx_p * ex + ny_p * ey) + nz_p * ez| / z_p;
+                       u_z = 1 + r * r
+           m = the largest of |c_p,k - c_q,k| over k (m = a_r; m = a_g > m ? a_g : m; the same with a_b);
+           r = m / d_p;  u_l = 1 + r * r
+           w = w_n / ((u_z * u_z) * (u_l * u_l))
+       that is, w_n * w_z * w_l with w_z = 1 / (1 + r_z^2)^2 and w_l = 1 / (1 + r_l^2)^2 behind one division.
+       k = (h[dy] * h[dx]) * w;  S = S + k;  C_k = C_k + k * c_q,k;  V = V + (k * k) * v_q
+       c'_k = C_k / S,  v' = V / (S * S).   S >= 9/64 because of the centre tap.
+   A stride larger than the image leaves the centre tap alone: the level is then the identity.
+
+   Output. After `levels` levels rgb = (float)min(1, c_k) and argb the render's packing of min(1, c_k). With
+   levels = 0 that is rt_accum_resolve, bit for bit. The filter does not fill pixels without samples in, and
+   it filters the colour as it is (no albedo demodulation): texture detail survives only as far as its
+   variance is small.
+
+   rt_denoise_run: host buffers (either may be NULL), blocking; it synchronises the stream of the
+   accumulator's last add first and runs there. rt_denoise_run_device: device buffers (either may be NULL),
+   asynchronous on hip_stream; ordering it against adds is the caller's job, and it allocates nothing. A run
+   never writes sum, sq or cnt. Runs of one denoiser share its planes and must not overlap. A run before any
+   add of any kind is RT_E_INVALID. rt_denoise_planes copies the last run's final planes out, after waiting
+   for that run: colour[3 * width * height] and variance[width * height] (either may be NULL); RT_E_INVALID
+   before any run.
+
+   Bad arguments are RT_E_INVALID with a message that starts with the entry's name, before the scene or a
+   device is touched; every entry restores the caller's current device. */
+typedef struct rt_denoise rt_denoise;
+typedef struct rt_denoise_params {
+  int32_t levels;      /* 0..8 a-trous levels, tap strides 1, 2, 4, ... */
+  int32_t normal_log2; /* 0..10: w_n = max(0, n_p . n_q) squared this many times (7: the power 128) */
+  double sigma_l;      /* > 0, finite: the colour edge-stop, in standard errors of the pixel's mean */
+  double sigma_z;      /* > 0, finite: the plane-distance edge-stop, relative to the hit's depth */
+} rt_denoise_params;
+int rt_denoise_defaults(rt_denoise_params* p);
+int rt_denoise_create(rt_accum* a, rt_denoise** out);
+int rt_denoise_guides(rt_denoise* d, float* normal, float* pos, float* depth, int32_t* material);
+int rt_denoise_run(rt_denoise* d, const rt_denoise_params* p, float* rgb, int32_t* argb);
+int rt_denoise_run_device(rt_denoise* d, const rt_denoise_params* p, float* d_rgb, int32_t* d_argb, void* hip_stream);
+int rt_denoise_planes(rt_denoise* d, double* colour, double* variance);
+void rt_denoise_destroy(rt_denoise* d);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,7 @@
 //
 //   rtrender <scene_dir> <file.cli> [-w W] [-h H] [-spp N] [-seed S] [-device D] [-o out.png]
 //            [-rgb out.f32] [-tex name=path.ppm]... [-time ITERS] [-nodir] [-budget MS] [-noise E [-max N]]
+//            [-denoise [LEVELS]]
 //
 // -budget MS: the best frame MS milliseconds give, in place of -spp's fixed count -- samples are accumulated
 // (rt_accum_*) in chunks of 2, 2, 4, 8, ... doubling up to 64 until the wall time since the first chunk was
@@ -14,6 +15,10 @@
 // that have fewer than N samples (default 1024) get 4, 8, 16, ... doubling up to 64 more, a chunk never taking
 // a pixel past N. Prints "pixels W*H samples TOTAL max MAXCOUNT" (the samples shaded in all and the largest
 // count of a pixel) and writes the resolved frame.
+//
+// -denoise [LEVELS]: the written frame is the denoised one (rt_denoise_*, the defaults with LEVELS a-trous levels
+// if given) instead of the resolved one. With -budget and -noise the accumulator of that mode also keeps the
+// moments; with a plain -spp N (N >= 2) the N samples go through a moments accumulator in one add.
 //
 // Without -o the image goes where myScene.saveFile puts it (myScene.java:1185-1196): the
 // `write` name (rt_scene_save_name) inside the folder "pics.<yyyy.MM.dd.hh.mm>" the scene
@@ -98,7 +103,7 @@ int main(int argc, char** argv) {
   if (argc < 3) {
     std::fprintf(stderr, "usage: %s <scene_dir> <file.cli> [-w W] [-h H] [-spp N] [-seed S] [-device D] "
                          "[-o out.png] [-rgb out.f32] [-tex name=path.ppm]... [-time ITERS] [-nodir] [-budget MS] "
-                         "[-noise E [-max N]]\n", argv[0]);
+                         "[-noise E [-max N]] [-denoise [LEVELS]]\n", argv[0]);
     return 2;
   }
   std::string dir = argv[1], cli = argv[2], out, rgbOut;
@@ -107,6 +112,8 @@ int main(int argc, char** argv) {
   double budgetMs = -1;  // >= 0: accumulate for that long instead of rendering spp samples
   double noise = -1;     // >= 0: sample adaptively down to that standard error
   int maxSamples = 1024;
+  bool denoise = false;
+  int denoiseLevels = -1;  // >= 0: that many levels instead of the default
   uint64_t seed = 0x5EED0001ull;
   std::vector<std::string> texNames, texPaths;
   for (int i = 3; i < argc; ++i) {
@@ -127,6 +134,10 @@ int main(int argc, char** argv) {
     else if (a == "-budget") budgetMs = std::atof(next().c_str());
     else if (a == "-noise") noise = std::atof(next().c_str());
     else if (a == "-max") maxSamples = std::atoi(next().c_str());
+    else if (a == "-denoise") {
+      denoise = true;
+      if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') denoiseLevels = std::atoi(argv[++i]);
+    }
     else if (a == "-tex") {
       std::string t = next();
       size_t eq = t.find('=');
@@ -167,6 +178,23 @@ int main(int argc, char** argv) {
   p.width = W; p.height = H; p.spp = spp; p.row0 = 0; p.row1 = H; p.row_step = 1; p.seed = seed;
   std::vector<float> rgb((size_t)W * H * 3);
   std::vector<int32_t> argb((size_t)W * H);
+  // the frame of an accumulator: resolved, or with -denoise the denoised one
+  auto frame = [&](rt_accum* acc) -> int {
+    if (!denoise) return rt_accum_resolve(acc, rgb.data(), argb.data());
+    rt_denoise* dn = nullptr;
+    rt_denoise_params dp;
+    int r = rt_denoise_defaults(&dp);
+    if (denoiseLevels >= 0) dp.levels = denoiseLevels;
+    if (r == 0) r = rt_denoise_create(acc, &dn);
+    if (r == 0) r = rt_denoise_run(dn, &dp, rgb.data(), argb.data());
+    rt_denoise_destroy(dn);
+    return r;
+  };
+  if (denoise && noise < 0 && budgetMs < 0 && spp < 2) {
+    std::fprintf(stderr, "-denoise expects -spp of at least 2, -budget or -noise\n");
+    rt_scene_destroy(s);
+    return 2;
+  }
   if (noise >= 0) {
     if (maxSamples < 1) { std::fprintf(stderr, "-max expects at least 1\n"); rt_scene_destroy(s); return 2; }
     rt_accum* acc = nullptr;
@@ -183,7 +211,7 @@ int main(int argc, char** argv) {
     }
     std::vector<int32_t> cnt((size_t)W * H);
     if (rc == 0) rc = rt_accum_counts(acc, cnt.data());
-    if (rc == 0) rc = rt_accum_resolve(acc, rgb.data(), argb.data());
+    if (rc == 0) rc = frame(acc);
     rt_accum_destroy(acc);
     if (rc) { std::fprintf(stderr, "rt_accum: %d %s\n", rc, rt_last_error()); rt_scene_destroy(s); return 1; }
     long long total = 0;
@@ -192,7 +220,7 @@ int main(int argc, char** argv) {
     std::printf("pixels %lld samples %lld max %d\n", (long long)W * H, total, most);
   } else if (budgetMs >= 0) {
     rt_accum* acc = nullptr;
-    rc = rt_accum_create(s, &p, 0, &acc);
+    rc = rt_accum_create(s, &p, denoise ? RT_ACCUM_MOMENTS : 0, &acc);
     int64_t n = 0;
     const auto t0 = std::chrono::steady_clock::now();
     for (int chunk = 2, first = 1; rc == 0; first = 0) {
@@ -201,10 +229,17 @@ int main(int argc, char** argv) {
       if (std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() > budgetMs) break;
       if (!first && chunk < 64) chunk *= 2;  // 2, 2, 4, 8, ... 64, 64, ...
     }
-    if (rc == 0) rc = rt_accum_resolve(acc, rgb.data(), argb.data());
+    if (rc == 0) rc = frame(acc);
     rt_accum_destroy(acc);
     if (rc) { std::fprintf(stderr, "rt_accum: %d %s\n", rc, rt_last_error()); rt_scene_destroy(s); return 1; }
     std::printf("samples %lld\n", (long long)n);
+  } else if (denoise) {
+    rt_accum* acc = nullptr;
+    rc = rt_accum_create(s, &p, RT_ACCUM_MOMENTS, &acc);
+    if (rc == 0) rc = rt_accum_add(acc, spp, nullptr);
+    if (rc == 0) rc = frame(acc);
+    rt_accum_destroy(acc);
+    if (rc) { std::fprintf(stderr, "rt_accum: %d %s\n", rc, rt_last_error()); rt_scene_destroy(s); return 1; }
   } else {
     rc = rt_render(s, &p, rgb.data(), argb.data());
     if (rc) { std::fprintf(stderr, "rt_render: %d %s\n", rc, rt_last_error()); rt_scene_destroy(s); return 1; }

@@ -127,6 +127,33 @@ DEVI T sload(const T* p) {
   static_assert(sizeof(T) == 4 || sizeof(T) == 8, "scalar field");
   return *(const __attribute__((address_space(4))) T*)p;
 }
+// Whole-record loads. The register-minimising scheduler places each field's s_load just ahead of its
+// first use, so one small record came in several dependent steps, each behind its own s_waitcnt
+// (a NodeF in two, a TriF in up to five). sload_vec reads N dwords (2, 4, 8, 16) at a wave-uniform,
+// 4-B aligned address as one vector: the load stays whole (the note above is about aggregates, not
+// vector types), and the record arrives behind one wait.
+// WREC<CNT, F> (RT_WREC, default 1, in the triangles-only kernels, F = 0, that do not count): NodeF, TriF and
+// the geometry of a TriD are read this way (sload_nodef, sload_trif, sload_tri). Every other kernel keeps
+// the field loads, and its code, as it was: the photon variant's allocation shifts with the new loads and
+// the counting kernel's scratch grows
+#ifndef RT_WREC
+#define RT_WREC 1
+#endif
+template <bool CNT, uint32_t F> static constexpr bool WREC = RT_WREC != 0 && !CNT && F == 0;
+template <int N>
+struct SVec {
+  typedef uint32_t T __attribute__((ext_vector_type(N), aligned(4)));
+};
+template <int N>
+DEVI typename SVec<N>::T sload_vec(const void* p) {
+  return *(const __attribute__((address_space(4))) typename SVec<N>::T*)p;
+}
+// two loads of one record made to complete at the same point: they are issued together and waited for
+// once, instead of the second being sunk behind the first one's wait to its own first use
+template <class A, class B>
+DEVI void sload_join(A& a, B& b) { asm volatile("" : "+s"(a), "+s"(b)); }
+DEVI float dw_f32(uint32_t v) { return __builtin_bit_cast(float, v); }
+DEVI double dw_f64(uint32_t lo, uint32_t hi) { return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo); }
 struct ChildBox {  // one child of a NodeD: box + reference
   double mn[3], mx[3];
   int32_t ref;
@@ -144,8 +171,27 @@ struct TriG {  // the part of a TriD the triangle test reads
   double n[3];
   double dA, dB;
 };
+template <bool W = false>
 DEVI TriG sload_tri(const TriD* t) {
   TriG g;
+  if constexpr (W) {
+    // two batches: the plane test's n, dA, dB (bytes 64..111, with v[2][2]) together, then the other
+    // eight vertex doubles as one load where the inside test needs them
+    static_assert(__builtin_offsetof(TriD, v) == 0 && __builtin_offsetof(TriD, n) == 72 && __builtin_offsetof(TriD, dA) == 96 &&
+                  __builtin_offsetof(TriD, dB) == 104, "TriD");
+    const char* b = reinterpret_cast<const char*>(t);
+    auto q = sload_vec<4>(b + 64);
+    auto p = sload_vec<8>(b + 80);
+    sload_join(q, p);
+    const auto v = sload_vec<16>(b);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) g.v[i / 3][i % 3] = dw_f64(v[2 * i], v[2 * i + 1]);
+    g.v[2][2] = dw_f64(q[0], q[1]);
+    g.n[0] = dw_f64(q[2], q[3]);
+    g.n[1] = dw_f64(p[0], p[1]); g.n[2] = dw_f64(p[2], p[3]);
+    g.dA = dw_f64(p[4], p[5]); g.dB = dw_f64(p[6], p[7]);
+    return g;
+  }
 #pragma unroll
   for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -276,8 +322,22 @@ DEVI TriRayF tri_ray_f32(V o, V d) {  // opaque: built per leaf, not hoisted and
 struct TriFR {  // a TriF, scalar-loaded
   float m[9], c[3], n[3], d, k, tm;
 };
+template <bool W = false>
 DEVI TriFR sload_trif(const TriF* p) {
   TriFR t;
+  if constexpr (W) {
+    static_assert(__builtin_offsetof(TriF, c) == 36 && __builtin_offsetof(TriF, n) == 48 && __builtin_offsetof(TriF, d) == 60 &&
+                  __builtin_offsetof(TriF, k) == 64 && __builtin_offsetof(TriF, tm) == 68, "TriF");
+    auto a = sload_vec<16>(p);  // m[9] c[3] n[3] d, then k tm
+    auto b = sload_vec<2>(reinterpret_cast<const char*>(p) + 64);
+    sload_join(a, b);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) t.m[i] = dw_f32(a[i]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { t.c[i] = dw_f32(a[9 + i]); t.n[i] = dw_f32(a[12 + i]); }
+    t.d = dw_f32(a[15]); t.k = dw_f32(b[0]); t.tm = dw_f32(b[1]);
+    return t;
+  }
 #pragma unroll
   for (int i = 0; i < 9; ++i) t.m[i] = sload(&p->m[0][0] + i);
 #pragma unroll
@@ -312,7 +372,7 @@ DEVI bool test_ref_u(const SceneD& S, int32_t ref, V o, V d, const Key& k, doubl
     if (!(F & FT_PRIM) || ref >= 0) {
       if (CNT) ct.c[C_TRI]++;
       WCNT(C_WTRI, 1);
-      const TriG T = sload_tri(S.tri + ref);
+      const TriG T = sload_tri<WREC<CNT, F>>(S.tri + ref);
       return tri_test<KN_SIGN<F>>(T, o, d, t, args, lim);
     }
   }
@@ -391,10 +451,10 @@ DEVI void leaf_closest(const SceneD& S, int32_t leaf, int accXf, V ao, V ad, WRa
     if (TF32 && (!(F & FT_PRIM) || ref >= 0) && xf == accXf && !w.moved) {  // test_ref_u's triangle case
       if (CNT) ct.c[C_TRI]++;
       WCNT(C_WTRI, 1);
-      const TriFR TF = sload_trif(S.triF + ref);
+      const TriFR TF = sload_trif<WREC<CNT, F>>(S.triF + ref);
       th = false;
       if (!tri_f32_out(TF, trf)) {
-        const TriG T = sload_tri(S.tri + ref);
+        const TriG T = sload_tri<WREC<CNT, F>>(S.tri + ref);
         th = tri_test<KN_SIGN<F>>(T, o, d, t, args, LimClosest{local, best.t});
       }
     } else {
@@ -678,8 +738,17 @@ struct NodeBoxF {  // a node's fp32 record, scalar-loaded
   float b[12];
   float mag, sl, sr;
 };
+template <bool W = false>
 DEVI NodeBoxF sload_nodef(const NodeF* p) {
   NodeBoxF n;
+  if constexpr (W) {
+    static_assert(__builtin_offsetof(NodeF, mag) == 48 && __builtin_offsetof(NodeF, sl) == 52 && __builtin_offsetof(NodeF, sr) == 56, "NodeF");
+    const auto a = sload_vec<16>(p);
+#pragma unroll
+    for (int i = 0; i < 12; ++i) n.b[i] = dw_f32(a[i]);
+    n.mag = dw_f32(a[12]); n.sl = dw_f32(a[13]); n.sr = dw_f32(a[14]);
+    return n;
+  }
 #pragma unroll
   for (int i = 0; i < 12; ++i) n.b[i] = sload(p->b + i);
   n.mag = sload(&p->mag); n.sl = sload(&p->sl); n.sr = sload(&p->sr);
@@ -840,7 +909,7 @@ DEVI void accel_closest_nf(const SceneD& S, const AccelD& A, V ao, V ad, RayInv 
       const NodeD* nd = S.node + N;
       // the fp32 pre-test on the node's 64-B fp32 record; the fp64 boxes are loaded only when a lane
       // is left unsettled (grazing rays, or a ray the pre-test cannot bound)
-      const NodeBoxF nb = sload_nodef(S.nodeF + N);
+      const NodeBoxF nb = sload_nodef<WREC<CNT, F>>(S.nodeF + N);
       struct { int32_t ref; } cl{sload_ref(nd, 0)}, cr{sload_ref(nd, 1)};
       WCNT(C_WNODE, 1);  // a node visit (8(d) prices one at 64 B, as the reference order's)
       bool hl = false, hr = false, ol = false, orr = false;
@@ -901,10 +970,10 @@ DEVI void accel_closest_nf(const SceneD& S, const AccelD& A, V ao, V ad, RayInv 
         WCNT(C_WTRI, 1);
         bool need = in_mask_t<MASKOPS<F>>(act);
         if (CNT && need) ct.c[C_TRI]++;
-        const TriFR TF = sload_trif(S.triF + st + i);  // the fp32 pre-test: a wave with every lane out skips the fp64 test
+        const TriFR TF = sload_trif<WREC<CNT, F>>(S.triF + st + i);  // the fp32 pre-test: a wave with every lane out skips the fp64 test
         if (need) need = !tri_f32_out(TF, trf);
         if (!__ballot(need)) continue;
-        const TriG T = sload_tri(S.tri + st + i);
+        const TriG T = sload_tri<WREC<CNT, F>>(S.tri + st + i);
         if (need) {
           double t;
           int args;
@@ -1212,10 +1281,10 @@ DEVI bool leaf_any(const SceneD& S, int32_t leaf, int accXf, V ao, V ad, WRay& w
     if (TF32 && (!(F & FT_PRIM) || ref >= 0) && xf == accXf && !w.moved) {  // test_ref_u's triangle case
       if (CNT) ct.c[C_TRI]++;
       WCNT(C_WTRI, 1);
-      const TriFR TF = sload_trif(S.triF + ref);
+      const TriFR TF = sload_trif<WREC<CNT, F>>(S.triF + ref);
       th = false;
       if (!tri_f32_out(TF, trf)) {
-        const TriG T = sload_tri(S.tri + ref);
+        const TriG T = sload_tri<WREC<CNT, F>>(S.tri + ref);
         th = tri_test<KN_SIGN<F>>(T, o, d, t, args, LimShadow{dist}) && (dist - t) > EPS;
       }
     } else {
@@ -1295,7 +1364,7 @@ DEVI bool accel_any_pk(const SceneD& S, const AccelD& A, V ao, V ad, WRay& w, co
       bool hl = false, hr = false;
       double el = DMAX, er = DMAX;
       const NodeD* nd = S.node + N;
-      const NodeBoxF nb = sload_nodef(S.nodeF + N);
+      const NodeBoxF nb = sload_nodef<WREC<CNT, F>>(S.nodeF + N);
       const struct { int32_t ref; } cl{sload_ref(nd, 0)}, cr{sload_ref(nd, 1)};
       bool ol = false, orr = false;
       if (in_mask_t<MASKOPS<F>>(act)) {

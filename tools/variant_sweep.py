@@ -76,6 +76,7 @@ VARIANTS = {  # name -> -D defines; names like "s12w4" are parsed (see defines_o
     "ru0": ["RT_RENORM_UNIT=0"], "dw0": ["RT_HIT_DW=0"], "ld0": ["RT_LIGHT_DIST=0"], "ps0": ["RT_PLANAR_SIGN=0"],
     "kn0": ["RT_RENORM_UNIT=0", "RT_HIT_DW=0", "RT_LIGHT_DIST=0", "RT_PLANAR_SIGN=0"],
     "hn0": ["RT_HIT_NRM=0"],                  # hit normals computed per hit, not read from the upload-time table
+    "wr0": ["RT_WREC=0"],                     # NodeF / TriF / TriD geometry as field loads, not whole-record loads
     "c4mr": ["@trace.hip:-Xarch_device", "@trace.hip:-mllvm=--amdgpu-sched-strategy=iterative-minreg",
              "@trace.hip:-Xarch_device", "@trace.hip:-mllvm=--amdgpu-use-amdgpu-trackers=1"],
 }

@@ -2097,9 +2097,10 @@ DEVI void photon_scan_any(const SceneD& S, const double* pos, double R2, Counter
 
 // The k nearest photons by selection instead of a heap (no per-lane memory): the
 // k-th smallest d^2 is bracketed by counting passes -- a histogram of equally spaced
-// buckets of the current window [lo, hi): 128 u8 buckets in LDS (knn_hist_pass; 64 u16 buckets
-// when a u8 bucket may have carried, KNN_EDGES = 16 u32 buckets when one lane has more than 65535
-// photons below hi) -- until the window holding the k-th
+// buckets of the current window [lo, hi): 128 u8 buckets in LDS (knn_hist_pass; the same 128
+// buckets through u16 counters, 64 at a time, when a u8 bucket may have carried, and through u32
+// ones, KNN_EDGES = 16 at a time, when one lane has more than 65535 photons below hi:
+// knn_hist_window) -- until the window holding the k-th
 // photon has <= KNN_SHELL photons; a last pass sums every photon below the window and
 // the nearest (k - below) window photons (kept sorted in registers). Same k-set and
 // largest d^2 as the heap; the powers are summed in scan order rather than the
@@ -2124,42 +2125,35 @@ DEVI void photon_scan_any(const SceneD& S, const double* pos, double R2, Counter
 #define RT_KNN_EDGES 16
 #endif
 static constexpr int KNN_SHELL = RT_KNN_SHELL;
-static constexpr int KNN_EDGES = RT_KNN_EDGES;  // u32 buckets of the last-resort counting pass
+static constexpr int KNN_EDGES = RT_KNN_EDGES;  // u32 buckets the last-resort counting pass takes at a time
 // The counting passes go through a per-lane LDS histogram (the traversal stack's pkT levels are idle
 // during shading): KNN_HB = 128 u8 buckets, four to a word, so a pass narrows the window 8x further
-// than 16 u32 ones (a carry is detected by the buckets' sum; such a lane repeats the pass with 64 u16
-// buckets, and with KNN_EDGES u32 ones past 65535 photons). Passes per gather call drop,
+// than 16 u32 ones (a carry is detected by the buckets' sum; such a lane counts the same buckets again
+// through u16 counters, and through u32 ones past 65535 photons: knn_hist_window). Passes per gather call drop,
 // C5 179.9 -> 175.0 ms against the u16 first pass, same image (profiles/r05n_c5_knn_h8_ab.log).
 static constexpr int KNN_HB = 128;
 static_assert(KNN_SHELL * 64 * 12 <= PK_LDS * 64 * 8, "window list fits the pkT levels");
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
 // One counting pass over [lo, hi) through a per-lane LDS histogram (packet kernels: the
-// traversal stack's pkT levels are idle during shading) of NB equally spaced buckets:
+// traversal stack's pkT levels are idle during shading) of NB equally spaced u8 buckets:
 // bucket j = #{k : e[k] <= d2} with e[k] = lo + (k + 1) w (k < NB - 1), e[NB - 1] = hi, and
 // the counts c(k) = photons with d2 < e[k] (including those under lo) are its prefix sums.
 // Yields c(NB - 1) (total) and the first edge kb with c(kb) >= K (-1: none), c(kb - 1) (0 for
-// kb = 0) and c(kb). P16: two u16 buckets per LDS word (NB = 64 in the same 8 KB as 16 u32
-// ones, so the first pass narrows 4x further); ovf reports more than 65535 photons below hi,
-// whose counts may have carried between the halves (the caller repeats the pass with u32).
-template <bool CNT, int NB, bool P16, bool P8 = false>
+// kb = 0) and c(kb). ovf: a bucket may have carried into its neighbour (the buckets' sum falls
+// short of the photons bucketed), or more photons than the test knob allows: the counts are void
+// and the caller counts again with knn_hist_window.
+template <bool CNT, int NB>
 DEVI void knn_hist_pass(const SceneD& S, const double* pos, double lo, double hi, int K, Counters& ct,
                         uint32_t& total, int& kb, uint32_t& cPrev, uint32_t& cAt, bool& ovf, bool lw = false) {
-  constexpr int NW = P8 ? NB / 4 : P16 ? NB / 2 : NB;  // LDS words per lane
+  constexpr int NW = NB / 4;  // LDS words per lane: four u8 buckets to a word
   static_assert(NW * 64 * 4 <= PK_LDS * 64 * 8, "histogram fits the pkT levels");
   lds_u32* hist = (lds_u32*)pkT() + __lane_id();
 #pragma unroll
   for (int q = 0; q < NW; ++q) hist[q * 64] = 0;
   uint32_t tot = 0;
   auto bump = [&](int j) {
-    if (P8) {
-      __hip_atomic_fetch_add(hist + (j >> 2) * 64, 1u << ((j & 3) * 8), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-      tot++;
-    } else if (P16) {
-      __hip_atomic_fetch_add(hist + (j >> 1) * 64, 1u << ((j & 1) * 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-      tot++;
-    } else {
-      __hip_atomic_fetch_add(hist + j * 64, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-    }
+    __hip_atomic_fetch_add(hist + (j >> 2) * 64, 1u << ((j & 3) * 8), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    tot++;
   };
   const double w = (hi - lo) * (1.0 / NB);
   const double inv = NB / (hi - lo);
@@ -2181,20 +2175,117 @@ DEVI void knn_hist_pass(const SceneD& S, const double* pos, double lo, double hi
       bump(j);
     }, lw);
   }
-  ovf = (P16 || P8) && tot > (uint32_t)S.knnU16Max;  // (the test knob lowers the u8 pass's limit too)
+  ovf = tot > (uint32_t)S.knnU16Max;  // (the test knob: as if the buckets had carried)
   uint32_t sum = 0;
   for (int q = 0; q < NW; ++q) {
     const uint32_t v = hist[q * 64];
 #pragma unroll
-    for (int h = 0; h < (P8 ? 4 : P16 ? 2 : 1); ++h) {
-      const uint32_t c = P8 ? ((v >> (8 * h)) & 0xffu) : P16 ? ((v >> (16 * h)) & 0xffffu) : v;
+    for (int h = 0; h < 4; ++h) {
+      const uint32_t c = (v >> (8 * h)) & 0xffu;
       const uint32_t run = total + c;
-      if (P8) sum += c;
-      if (kb < 0 && (int)run >= K) { kb = P8 ? 4 * q + h : P16 ? 2 * q + h : q; cPrev = total; cAt = run; }
+      sum += c;
+      if (kb < 0 && (int)run >= K) { kb = 4 * q + h; cPrev = total; cAt = run; }
       total = run;
     }
   }
-  if (P8 && sum != tot) ovf = true;  // a u8 carry: the buckets' sum falls short by 255 (256 out of a word)
+  if (sum != tot) ovf = true;  // a u8 carry: the buckets' sum falls short by 255 (256 out of a word)
+}
+
+// A lane whose u8 buckets cannot hold its counts counts again on the SAME KNN_HB-bucket grid, the NBW
+// buckets [base, base + NBW) at a time through wider counters (64 u16, then KNN_EDGES u32 ones past
+// 65535 photons): photons of lower buckets are only tallied, those of higher ones only counted in
+// the total. The lane so ends the pass on the window the u8 buckets would have given: the final
+// window, and with it the order the powers are summed in, does not depend on which counters
+// counted (DISTRAYTRACER_KNN_U16_MAX changes no bit of the result). total = photons below hi; kb
+// (-1 when c(base + NBW - 1) < K: look higher; -2 when c(base - 1) >= K: look lower), c(kb - 1) and
+// c(kb) as knn_hist_pass; ovf (P16): more than the u16 limit below hi, the counts are void. The
+// caller starts at the part the voided u8 counts point to (a carry moves them by a bucket at most
+// here and there), so one scan settles nearly every such pass, as the whole-window passes did.
+template <bool CNT, int NBW, bool P16>
+DEVI void knn_hist_window(const SceneD& S, const double* pos, double lo, double hi, int K, Counters& ct, int base,
+                          uint32_t& total, int& kb, uint32_t& cPrev, uint32_t& cAt, bool& ovf, bool lw) {
+  constexpr int NB = KNN_HB;
+  constexpr int NW = P16 ? NBW / 2 : NBW;  // LDS words per lane
+  static_assert(NW * 64 * 4 <= PK_LDS * 64 * 8 && NB % NBW == 0, "histogram fits the pkT levels");
+  lds_u32* hist = (lds_u32*)pkT() + __lane_id();
+#pragma unroll
+  for (int q = 0; q < NW; ++q) hist[q * 64] = 0;
+  uint32_t tot = 0, under = 0;
+  auto bump = [&](int j) {
+    tot++;
+    j -= base;
+    if (j < 0) under++;
+    else if (j < NBW) {
+      if (P16) __hip_atomic_fetch_add(hist + (j >> 1) * 64, 1u << ((j & 1) * 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+      else __hip_atomic_fetch_add(hist + j * 64, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    }
+  };
+  // the bucket of a photon exactly as knn_hist_pass forms it
+  const double w = (hi - lo) * (1.0 / NB);
+  const double inv = NB / (hi - lo);
+  const bool narrow = !((hi - lo) > hi * 0x1p-30);
+  if (!__ballot(narrow)) {
+    const double lob = lo + 0x1p-12 * w;
+    photon_scan_any<CNT>(S, pos, hi, ct, [&](double d2, int, V) {
+      const int j0 = (int)fmax((d2 - lob) * inv, 0.0);
+      bump(min(j0 + ((d2 < lo + (j0 + 1) * w) ? 0 : 1), NB - 1));
+    }, lw);
+  } else {
+    photon_scan_any<CNT>(S, pos, hi, ct, [&](double d2, int, V) {
+      int j = 0;
+      while (j < NB - 1 && !(d2 < lo + (j + 1) * w)) ++j;
+      bump(j);
+    }, lw);
+  }
+  ovf = P16 && tot > (uint32_t)S.knnU16Max;
+  total = tot;
+  uint32_t run = under;
+  kb = (int)under >= K ? -2 : -1;  // -2: the k-th photon lies in a lower bucket than base
+  for (int q = 0; q < NW; ++q) {
+    const uint32_t v = hist[q * 64];
+#pragma unroll
+    for (int h = 0; h < (P16 ? 2 : 1); ++h) {
+      const uint32_t prev = run;
+      run += P16 ? ((v >> (16 * h)) & 0xffffu) : v;
+      if (kb == -1 && (int)run >= K) { kb = base + (P16 ? 2 * q + h : q); cPrev = prev; cAt = run; }
+    }
+  }
+}
+
+// The timed kernels reach knn_hist_window through a real (noinline) call, as they reach knn_java_: the
+// rare path stays out of the hot variants' code and register allocation (inlined it cost C5 1.4 %).
+// The call takes and returns plain values -- (total | ovf << 31, kb, c(kb - 1), c(kb)) -- so nothing
+// of the caller's is address-taken; the counting kernels (CNT) keep the inlined form, whose scans
+// count into the caller's counters.
+typedef uint32_t knn_u32x4 __attribute__((ext_vector_type(4)));
+template <int NBW, bool P16>
+__device__ __attribute__((noinline)) knn_u32x4 knn_hist_window_(const NodeD* pnode, const double* ppos, int32_t root, int32_t u16max,
+                                                                double px, double py, double pz, double lo, double hi, int K,
+                                                                int base, bool lw) {
+  SceneD T;  // the fields a counting scan reads
+  T.pnode = pnode; T.ppos = ppos; T.ppwr = ppos; T.photonRoot = root; T.knnU16Max = u16max;
+  const double pos[3] = {px, py, pz};
+  Counters ct;
+  uint32_t total = 0, cPrev = 0, cAt = 0;
+  int kb = -1;
+  bool ovf = false;
+  knn_hist_window<false, NBW, P16>(T, pos, lo, hi, K, ct, base, total, kb, cPrev, cAt, ovf, lw);
+  knn_u32x4 r;
+  r.x = total | (ovf ? 0x80000000u : 0u); r.y = (uint32_t)kb; r.z = cPrev; r.w = cAt;
+  return r;
+}
+template <bool CNT, int NBW, bool P16>
+DEVI void knn_hist_window_call(const SceneD& S, const double* pos, double lo, double hi, int K, Counters& ct, int base,
+                               uint32_t& total, int& kb, uint32_t& cPrev, uint32_t& cAt, bool& ovf, bool lw) {
+  if constexpr (CNT) {
+    knn_hist_window<true, NBW, P16>(S, pos, lo, hi, K, ct, base, total, kb, cPrev, cAt, ovf, lw);
+  } else {
+    const knn_u32x4 r = knn_hist_window_<NBW, P16>(S.pnode, S.ppos, S.photonRoot, S.knnU16Max, pos[0], pos[1], pos[2], lo, hi,
+                                                   K, base, lw);
+    total = r.x & 0x7fffffffu;
+    ovf = (r.x >> 31) != 0;
+    kb = (int)r.y; cPrev = r.z; cAt = r.w;
+  }
 }
 
 // Exact replay of the reference's neighbourhood for ONE lane whose k-th distance is tied (several
@@ -2354,26 +2445,29 @@ DEVI V irradiance(const SceneD& S, V p, Counters& ct) {
   for (int level = 0; level < 32; ++level) {
     PROF_T0(t_kc);
     constexpr int NE = KNN_EDGES;
-    // c(k) = photons with d2 < e[k] (including the `below` ones); the pass yields c(NE - 1)
+    // c(k) = photons with d2 < e[k] (including the `below` ones); the pass yields c(KNN_HB - 1)
     // and the first edge kb with c(kb) >= K (-1: none), c(kb - 1) (0 for kb = 0) and c(kb)
     uint32_t total = 0, cPrev = 0, cAt = 0;
     int kb = -1;
-    int ne = NE;  // this lane's edges in this pass: e[k] = lo + (k + 1) w, w = (hi - lo) / ne
     bool ovf = false;
-    knn_hist_pass<CNT, KNN_HB, false, true>(S, pos, lo, hi, K, ct, total, kb, cPrev, cAt, ovf, lw);
-    ne = KNN_HB;
-    if (__ballot(ovf)) {  // a u8 bucket may have carried: this pass again with u16 buckets
+    knn_hist_pass<CNT, KNN_HB>(S, pos, lo, hi, K, ct, total, kb, cPrev, cAt, ovf, lw);
+    if (__ballot(ovf)) {  // a u8 bucket may have carried: the same 128 buckets again, 64 at a time in u16
       if (ovf) {
-        total = cPrev = cAt = 0; kb = -1; ovf = false;
-        knn_hist_pass<CNT, 64, true>(S, pos, lo, hi, K, ct, total, kb, cPrev, cAt, ovf, lw);
-        ne = 64;
-      }
-    }
-    if (__ballot(ovf)) {  // > 65535 photons below hi: this pass again with u32 buckets
-      if (ovf) {
-        total = cPrev = cAt = 0; kb = -1;
-        knn_hist_pass<CNT, NE, false>(S, pos, lo, hi, K, ct, total, kb, cPrev, cAt, ovf, lw);
-        ne = NE;
+        bool big = false;
+        const int g = kb;  // the u8 counts' answer: void, but where to look first
+        for (int base = g >= 64 ? 64 : 0, i = 0; i < KNN_HB / 64; ++i) {
+          knn_hist_window_call<CNT, 64, true>(S, pos, lo, hi, K, ct, base, total, kb, cPrev, cAt, big, lw);
+          if (big || (int)total < K || kb >= 0) break;
+          base += kb == -2 ? -64 : 64;
+        }
+        if (big) {  // > 65535 photons below hi: NE at a time in u32
+          for (int base = g < 0 ? KNN_HB - NE : g & ~(NE - 1), i = 0; i < KNN_HB / NE; ++i) {
+            knn_hist_window_call<CNT, NE, false>(S, pos, lo, hi, K, ct, base, total, kb, cPrev, cAt, big, lw);
+            if ((int)total < K || kb >= 0) break;
+            base += kb == -2 ? -NE : NE;
+          }
+        }
+        if ((int)total < K) kb = -1;
       }
     }
     PROF_ADD(t_kc, R_KNN_COUNT);
@@ -2382,16 +2476,19 @@ DEVI V irradiance(const SceneD& S, V p, Counters& ct) {
       if (hi == R2max) { all = true; break; }
       // every photon under hi is in the set: the window moves above it, and grows by the
       // surface-density extrapolation (count ~ d^2) of what is still missing, at most to R2far
-      const double ext = total > 0 ? hi * (RT_KNN_START * K / (double)total) : R2far;
+      // (never less than the density estimate itself, K / total > 1: with a start factor below 1 the
+      // "widened" window ended below its own bottom and the set came out wrong)
+      constexpr double kExt = RT_KNN_START < 1.0 ? 1.0 : RT_KNN_START;
+      const double ext = total > 0 ? hi * (kExt * K / (double)total) : R2far;
       lo = hi;
       below = (int)total;
       hi = (hi < R2far) ? fmin(R2far, ext) : R2max;
       continue;
     }
-    // the window becomes [e[kb - 1], e[kb]) with e[k] = lo + (k + 1) w, e[ne - 1] = hi (the
-    // pass's w: (hi - lo) / ne, an exact power-of-two scaling either way)
-    const double wp = (hi - lo) * (ne == NE ? 1.0 / NE : ne == 64 ? 1.0 / 64 : 1.0 / 128);
-    const double nhi = (kb == ne - 1) ? hi : lo + (kb + 1) * wp;
+    // the window becomes [e[kb - 1], e[kb]) with e[k] = lo + (k + 1) w, e[KNN_HB - 1] = hi (the
+    // pass's w: (hi - lo) / KNN_HB, an exact power-of-two scaling; the same grid whichever counters counted)
+    const double wp = (hi - lo) * (1.0 / KNN_HB);
+    const double nhi = (kb == KNN_HB - 1) ? hi : lo + (kb + 1) * wp;
     const double nlo = kb ? lo + kb * wp : lo;
     const int nbelow = kb ? (int)cPrev : below, cb = (int)cAt;
     lo = nlo; hi = nhi; below = nbelow;

@@ -207,6 +207,20 @@ def jdiv(a, b):
     return math.copysign(math.inf, a) * math.copysign(1.0, b)
 
 
+def jsqrt(x):
+    """Java's square root (the reference writes Math.pow(x, .5)): NaN for a negative or NaN argument,
+    where Python's `** .5` hands back a complex number."""
+    return math.sqrt(x) if x >= 0 else math.nan
+
+
+def jacos(x):  # Math.acos: NaN outside [-1, 1] (Python raises)
+    return math.acos(x) if -1 <= x <= 1 else math.nan
+
+
+def jasin(x):  # Math.asin
+    return math.asin(x) if -1 <= x <= 1 else math.nan
+
+
 def jmax(vals):  # DistRayTracer.max (:420): NaN never replaces
     m = -1.7976931348623157e308
     for v in vals:
@@ -224,7 +238,7 @@ def jmin(vals):  # DistRayTracer.min (:421)
 
 
 def angle_between(v1, v2):  # DistRayTracer._angleBetween (:445-452)
-    return math.acos(dot(v1, v2) / (mag(v1) * mag(v2)))
+    return jacos(jdiv(dot(v1, v2), mag(v1) * mag(v2)))
 
 
 def rot_axis(v1, u, th):  # DistRayTracer.rotVecAroundAxis (:336-349)
@@ -346,6 +360,8 @@ def shader_from_tokens(tok, simple_flag):
     f = [float(x) for x in tok[1:]]
     if tok[0] == "diffuse":
         return Shader(f[0:3], f[3:6], (0, 0, 0), 0.0, 0.0, simple=simple_flag)
+    if tok[0] == "reflective":  # myRTFileReader.java:209-217: `diffuse` with a KRefl
+        return Shader(f[0:3], f[3:6], (0, 0, 0), 0.0, f[6], simple=simple_flag)
     kt = f[11] if len(f) > 11 else 0.0
     perm = f[12] if len(f) > 12 else 0.0
     pc = tuple(f[13:16]) if len(f) > 15 else (perm, perm, perm)
@@ -371,7 +387,7 @@ class Sphere:  # mySphere (myImpObject.java:35-94)
         discr = ((b * b) - (2 * ta * cc))
         if discr < 0:
             return None
-        d1 = discr ** .5
+        d1 = jsqrt(discr)
         t1, t2 = (-1 * b + d1) / ta, (-1 * b - d1) / ta
         tv = min(t1, t2)
         if tv < EPS:
@@ -1082,11 +1098,13 @@ class Scene:
         self.viewZ = -1 * (max(H, W) / 2.0) / math.tan(fov_rad / 2)
 
     # findClosestRayHit (myScene.java:888-903): the TreeMap keeps the first hit of an equal t
+    # the map starts with rayHit(false) at t = Double.MAX_VALUE (:891), so a hit whose t is NaN sorts
+    # after it (Double.compare) and the ray misses
     def closest(self, ray):
         best = None
         for obj in self.objs:
             h = obj.intersect(ray, ray.transformed(obj.ctm[1]), obj.ctm)
-            if h is not None and (best is None or h.t < best.t):
+            if h is not None and h.t < (1.7976931348623157e308 if best is None else best.t):
                 best = h
         return best
 
@@ -1116,8 +1134,8 @@ class Scene:
             t = dist(sray.o, xpt(L.ctm[0], L.position(lk, 2)))                      # intersectCheck :33-41
             lt_mult = 1.0
             if L.kind == "spot":                                                    # :159-163, calcT_Mult :79-82
-                angle = math.acos(-1 * dot(sray.d, L.orient))
-                lt_mult = 1 if angle < L.inner else 0 if angle > L.outer else (L.outer - angle) / L.rad_diff
+                angle = jacos(-1 * dot(sray.d, L.orient))
+                lt_mult = 1 if angle < L.inner else 0 if angle > L.outer else jdiv(L.outer - angle, L.rad_diff)
             TRACE.append(("light", L.kind, L.index, h.trans_ray.node, lt_mult))
             if lt_mult == 0:
                 continue
@@ -1172,24 +1190,24 @@ class Scene:
         idx = sh.perm if sh.simple else sh.ktrans          # simple: currPerm as the index (:546,563)
         n, n1, n2, cos2, tr, omtr, TIR = 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, False
         if rnm < 0:                                        # leaving (:196-212 / :544-560)
-            if thetaI < math.asin(1.0 / idx):
+            if thetaI < jasin(1.0 / idx):
                 n1, n2 = idx, 1.0
                 n = n1 / n2
-                cos2 = (1.0 - (n * n) * (1.0 - (cos1 * cos1))) ** .5
+                cos2 = jsqrt(1.0 - (n * n) * (1.0 - (cos1 * cos1)))
             else:
                 tr, omtr, TIR, cos2 = 1.0, 0.0, True, 0.0
         else:                                              # entering (:213-222 / :561-570)
             n1 = h.trans_ray.kt[1] if sh.simple else h.trans_ray.kt[0]
             n2 = idx
             n = n1 / n2
-            cos2 = (1.0 - (n * n) * (1.0 - (cos1 * cos1))) ** .5
+            cos2 = jsqrt(1.0 - (n * n) * (1.0 - (cos1 * cos1)))
         if not TIR:                                        # Fresnel, Q15 (:224-231 / :573-580)
-            sa = math.sin(math.acos(cos1))
-            rct = (1.0 - ((n1 / n2) * sa * sa)) ** .5
+            sa = math.sin(jacos(cos1))
+            rct = jsqrt(1.0 - ((n1 / n2) * sa * sa))
             a1, b1 = n1 * cos1, n2 * rct
-            nd1 = (a1 - b1) / (a1 + b1)                    # calcFresPerp :78-81
+            nd1 = jdiv(a1 - b1, a1 + b1)                   # calcFresPerp :78-81
             a2, b2 = n1 * rct, n2 * cos1
-            nd2 = (a2 - b2) / (a2 + b2)                    # calcFresPlel :83-86
+            nd2 = jdiv(a2 - b2, a2 + b2)                   # calcFresPlel :83-86
             tr = ((nd1 * nd1) + (nd2 * nd2)) / 2.0
             omtr = 1 - tr
         TRACE.append(("fresnel", "simple" if sh.simple else "full", "leave" if rnm < 0 else "enter", TIR, tr,
@@ -1309,7 +1327,7 @@ def load(cli_text, W, H, scene_dir=None, textures=None):
 
     objs, lights, bg, fov = [], [], (0.0, 0.0, 0.0), 90.0
     shader, simple_flag, poly = None, False, None
-    top = IDENT                                   # matrixStack.peek()
+    top, stack = IDENT, []                        # matrixStack.peek() and what lies under it
     tex, photons = None, None                     # currTextureTop (txtrType 1) / the photon command
     ts = TextureState()                           # txtrType and the procedural texture fields
     tmp_list = None                               # begin_list ... end_accel (addToTmpListIDX)
@@ -1341,7 +1359,7 @@ def load(cli_text, W, H, scene_dir=None, textures=None):
         elif c == "disk_light":
             lights.append(Light("disk", len(lights), map(float, tok[1:4]), map(float, tok[8:11]),
                                 map(float, tok[5:8]), radius=float(tok[4]), ctm=ctm_ara(top)))
-        elif c in ("diffuse", "shiny", "surface"):
+        elif c in ("diffuse", "reflective", "shiny", "surface"):
             if c == "shiny" and len(tok) > 12 and (float(tok[12]) > 0 or (len(tok) > 13 and float(tok[13]) > 0)):
                 simple_flag = True  # scFlags[simpleRefrIDX] stays set for the rest of the scene (:377)
             shader = shader_from_tokens(tok, simple_flag)
@@ -1369,6 +1387,10 @@ def load(cli_text, W, H, scene_dir=None, textures=None):
             T = Matrix()
             T.m[0][3], T.m[1][3], T.m[2][3] = float(tok[1]), float(tok[2]), float(tok[3])
             top = top.mult_mat(T)
+        elif c == "push":                        # gtPushMatrix (myScene.java:1241-1246): the top, duplicated
+            stack.append(top)
+        elif c == "pop":                         # gtPopMatrix (:1248-1254)
+            top = stack.pop()
         elif c == "sphere":
             objs_ctm = ctm_ara(top)
             add(Sphere(float(tok[1]), [float(x) for x in tok[2:5]], cur_shader(), objs_ctm))

@@ -267,7 +267,10 @@ def _tile_major(W, H):
     return np.array(out, dtype=np.int32)
 
 
-@pytest.mark.parametrize("W,H", [(13, 11), (70, 9)])
+# Past 256 tiles select_scan_kernel's 256 threads take ceil(ntiles / 256) counts each: 2056 x 8 and 8 x 2056 are 257
+# tiles (two a thread, thread 128 half-filled, threads 129.. empty), 136 x 136 is 289. The masks in the loop below are a
+# random one, the full one and a checkerboard, each followed by the empty one.
+@pytest.mark.parametrize("W,H", [(13, 11), (70, 9), (2056, 8), (8, 2056), (136, 136)])
 def test_selection_is_the_mask_in_tile_major_order(scene_of, W, H):
     import torch
 

@@ -36,7 +36,7 @@ OBJ_DIR = LIB_DIR / "obj"
 SOURCE_FLAGS = {"render_minreg.hip": ["-Xarch_device", "-mllvm=--amdgpu-sched-strategy=iterative-minreg",
                                       "-Xarch_device", "-mllvm=--amdgpu-use-amdgpu-trackers=1"]}
 HEADERS = ["rt_types.h", "rt_internal.h", "comm.h", "host_math.h", "trace_device.h", "trace_kernels.h", "query_kernels.h", "shade_kernels.h", "accum_kernels.h", "accum_state.h", "adaptive_kernels.h", "denoise_kernels.h", "camera_ray.h",
-           "wavefront.h", "qdiv.h", "jfdlibm.h"]
+           "wavefront.h", "launch_common.h", "qdiv.h", "jfdlibm.h"]
 # -ffp-contract=off: keep the reference's (Java) unfused double arithmetic so discrete
 # decisions (hits, shadows, TIR) match the oracle; no fast-math (IEEE Inf/NaN needed).
 COMPILE_FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math",

@@ -3,10 +3,10 @@
 // frame so far, ask how noisy it still is, checkpoint it and go on. The kernels (accum_kernels.h) run the
 // render kernel's wave layout and shading tree (trace_sample) and are instantiated here, in a translation
 // unit of their own, so that the register allocation of the kernels in the other units is not disturbed.
+// The host plumbing shared with the other units (HIP check, variant lookup, staging) is launch_common.h's.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
-#include <mutex>
 #include <string>
 
 // as render_minreg.hip: trace.hip alone holds the kernels trace_kernels.h defines outright
@@ -15,19 +15,13 @@
 #include "comm.h"
 #include "accum_state.h"
 #include "accum_kernels.h"
+#define RT_UNIT_SHADES  // the kernels reach the noise textures: this unit uploads its own Perlin tables
+#include "launch_common.h"
 
 using namespace rt;
 
-#define HIPCHK(expr)                                                                    \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess)                                                               \
-      return set_error(RT_E_HIP, std::string(#expr " failed: ") + hipGetErrorString(e_)); \
-  } while (0)
-
 namespace {
 
-constexpr uint32_t F_C4 = dv::FT_PRIM | dv::FT_TRANS | dv::FT_TEX | dv::FT_LIGHTX;
 constexpr uint32_t RENDER_FLAGS = RT_RENDER_GENERIC | RT_RENDER_NOCULL;
 constexpr uint32_t ACCUM_FLAGS = RT_ACCUM_MOMENTS | RT_ACCUM_COUNTS;
 
@@ -37,32 +31,10 @@ struct AccumVariant {
   AccumFn fn[2];  // without / with the square sums
 };
 #define AV(F) {F, {dv::accum_kernel<F, false>, dv::accum_kernel<F, true>}}
-// the masks of query.hip's kQueryVariants, picked by the same rule: the specialised shading tree the scene's
-// render runs where one matches exactly, else the generic one
-const AccumVariant kAccumVariants[] = {AV(0u), AV(F_C4), AV(dv::F_C5), AV((uint32_t)dv::FT_ALL)};
+// the specialised shading tree the scene's render runs where one matches exactly, else the generic one
+// (launch_common.h variant_for)
+const AccumVariant kAccumVariants[] = {RT_VARIANT_MASKS(AV)};
 #undef AV
-
-const AccumVariant& accum_variant(const rt_scene* s, uint32_t render_flags) {
-  const uint32_t m = render_variant_mask(s, render_flags & RT_RENDER_GENERIC);
-  for (const AccumVariant& v : kAccumVariants)
-    if (v.mask == m) return v;
-  return kAccumVariants[sizeof(kAccumVariants) / sizeof(kAccumVariants[0]) - 1];
-}
-
-// this unit's copy of the Perlin tables (trace_kernels.h c_perm / c_grad3), uploaded once per device before
-// the first launch there (the current device is the scene's), as shade.hip does for its own
-int perlin_ready(int device) {
-  static std::mutex mu;
-  static bool done[64] = {};
-  std::lock_guard<std::mutex> lk(mu);
-  if (device >= 0 && device < 64 && done[device]) return RT_OK;
-  const int *perm = nullptr, *grad3 = nullptr;
-  perlin_tables(&perm, &grad3);
-  HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(dv::c_perm), perm, sizeof(int) * 256));
-  HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(dv::c_grad3), grad3, sizeof(int) * 36));
-  if (device >= 0 && device < 64) done[device] = true;
-  return RT_OK;
-}
 
 size_t sums_bytes(const rt_accum* a) { return (size_t)3 * (size_t)a->W * (size_t)a->H * sizeof(double); }
 int64_t pixels(const rt_accum* a) { return (int64_t)a->W * a->H; }
@@ -129,12 +101,9 @@ int read_back(rt_accum* a, void* host, size_t bytes, Fill fill) {
   int rc = fill(d);
   hipError_t e = hipSuccess;
   if (rc == RT_OK) e = hipMemcpyAsync(host, d, bytes, hipMemcpyDeviceToHost, (hipStream_t)a->last);
-  const hipError_t se = hipStreamSynchronize((hipStream_t)a->last);
+  rc = sync_report((hipStream_t)a->last, rc, e, "rt_accum read-back: ", "rt_accum kernel: ");
   (void)hipFree(d);
-  if (rc != RT_OK) return rc;
-  if (e != hipSuccess) return set_error(RT_E_HIP, std::string("rt_accum read-back: ") + hipGetErrorString(e));
-  if (se != hipSuccess) return set_error(RT_E_HIP, std::string("rt_accum kernel: ") + hipGetErrorString(se));
-  return RT_OK;
+  return rc;
 }
 
 }  // namespace
@@ -165,11 +134,8 @@ int rt_accum_create(rt_scene* s, const rt_render_params* p, uint32_t accum_flags
   if (rc) return set_error(rc, w + ": " + rt_last_error());
   HIPCHK(hipSetDevice(s->device));
   if ((rc = perlin_ready(s->device)) != RT_OK) return rc;
-  if (!s->stream) {
-    hipStream_t st;
-    HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    s->stream = st;
-  }
+  hipStream_t st;
+  if ((rc = scene_stream(s, &st)) != RT_OK) return rc;
   rt_accum* a = new rt_accum();
   a->flags = accum_flags;
   a->W = p->width;
@@ -179,7 +145,7 @@ int rt_accum_create(rt_scene* s, const rt_render_params* p, uint32_t accum_flags
   a->rp = q;
   a->sum = nullptr;
   a->sq = nullptr;
-  a->last = s->stream;
+  a->last = st;
   hipError_t e = hipMalloc(&a->sum, sums_bytes(a));
   if (e == hipSuccess && (accum_flags & RT_ACCUM_MOMENTS)) e = hipMalloc(&a->sq, sums_bytes(a));
   if (e == hipSuccess && (accum_flags & RT_ACCUM_COUNTS) && adaptive_alloc(a) != RT_OK) e = hipErrorOutOfMemory;
@@ -218,7 +184,7 @@ int rt_accum_add(rt_accum* a, int count, void* hip_stream) {
     a->last = st;
     return RT_OK;
   }
-  const AccumVariant& v = accum_variant(s, a->rp.flags);
+  const AccumVariant& v = variant_for(kAccumVariants, render_variant_mask(s, a->rp.flags));
   const int64_t tilesX = (P.W + P.tw - 1) / P.tw, tilesY = (P.H + P.th - 1) / P.th;
   if (tilesX * tilesY > INT32_MAX) return set_error(RT_E_INVALID, w + ": more than 2^31 - 1 tiles");
   hipLaunchKernelGGL(v.fn[a->sq ? 1 : 0], dim3((unsigned)(tilesX * tilesY)), dim3(64), dv::LDS_RENDER_BYTES, st, sd, P, (int)a->done,

@@ -2,11 +2,11 @@
 // accumulator with RT_ACCUM_COUNTS keeps a sample count per pixel, so a host can select the pixels that are
 // still noisy and add samples to those alone. The kernels (adaptive_kernels.h) are instantiated here, in a
 // translation unit of their own, so that the register allocation of accum.hip's kernels is not disturbed.
+// The host plumbing shared with the other units (HIP check, variant lookup, staging) is launch_common.h's.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
-#include <mutex>
 #include <string>
 
 // as render_minreg.hip: trace.hip alone holds the kernels trace_kernels.h defines outright
@@ -15,19 +15,12 @@
 #include "comm.h"
 #include "accum_state.h"
 #include "adaptive_kernels.h"
+#define RT_UNIT_SHADES  // the kernels reach the noise textures: this unit uploads its own Perlin tables
+#include "launch_common.h"
 
 using namespace rt;
 
-#define HIPCHK(expr)                                                                    \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess)                                                               \
-      return set_error(RT_E_HIP, std::string(#expr " failed: ") + hipGetErrorString(e_)); \
-  } while (0)
-
 namespace {
-
-constexpr uint32_t F_C4 = dv::FT_PRIM | dv::FT_TRANS | dv::FT_TEX | dv::FT_LIGHTX;
 
 typedef void (*ListFn)(SceneD, ParamsD, const int32_t*, size_t, int32_t*, double*, double*);
 struct ListVariant {
@@ -35,31 +28,9 @@ struct ListVariant {
   ListFn fn[2];  // without / with the square sums
 };
 #define LV(F) {F, {dv::accum_list_kernel<F, false>, dv::accum_list_kernel<F, true>}}
-// accum.hip's kAccumVariants, picked by the same rule
-const ListVariant kListVariants[] = {LV(0u), LV(F_C4), LV(dv::F_C5), LV((uint32_t)dv::FT_ALL)};
+// the variant accum.hip's kAccumVariants gives the same scene (launch_common.h variant_for)
+const ListVariant kListVariants[] = {RT_VARIANT_MASKS(LV)};
 #undef LV
-
-const ListVariant& list_variant(const rt_scene* s, uint32_t render_flags) {
-  const uint32_t m = render_variant_mask(s, render_flags & RT_RENDER_GENERIC);
-  for (const ListVariant& v : kListVariants)
-    if (v.mask == m) return v;
-  return kListVariants[sizeof(kListVariants) / sizeof(kListVariants[0]) - 1];
-}
-
-// this unit's copy of the Perlin tables (trace_kernels.h c_perm / c_grad3), uploaded once per device before
-// the first launch there (the current device is the scene's), as accum.hip does for its own
-int perlin_ready(int device) {
-  static std::mutex mu;
-  static bool done[64] = {};
-  std::lock_guard<std::mutex> lk(mu);
-  if (device >= 0 && device < 64 && done[device]) return RT_OK;
-  const int *perm = nullptr, *grad3 = nullptr;
-  perlin_tables(&perm, &grad3);
-  HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(dv::c_perm), perm, sizeof(int) * 256));
-  HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(dv::c_grad3), grad3, sizeof(int) * 36));
-  if (device >= 0 && device < 64) done[device] = true;
-  return RT_OK;
-}
 
 int64_t pixels(const rt_accum* a) { return (int64_t)a->W * a->H; }
 int tiles_x(const rt_accum* a) { return (a->W + dv::SEL_TILE - 1) / dv::SEL_TILE; }
@@ -109,7 +80,7 @@ int launch_list(rt_accum* a, const ParamsD& P, const int32_t* list, int64_t nlis
   int rc = perlin_ready(s->device);
   if (rc != RT_OK) return rc;
   const SceneD sd = render_scene_view(s, a->rp.flags & RT_RENDER_NOCULL);
-  const ListVariant& v = list_variant(s, a->rp.flags);
+  const ListVariant& v = variant_for(kListVariants, render_variant_mask(s, a->rp.flags));
   hipLaunchKernelGGL(v.fn[a->sq ? 1 : 0], dim3((unsigned)blocks), dim3(64), dv::LDS_RENDER_BYTES, st, sd, P, list, (size_t)nlist, a->cnt,
                      a->sum, a->sq);
   HIPCHK(hipGetLastError());

@@ -3,6 +3,7 @@
 // guided by the normal, position, depth and material of exactly the frame's centre rays. The guides come from
 // the entries a host would use (rt_camera_rays_device, rt_trace_rays_device); the kernels (denoise_kernels.h)
 // live in this translation unit alone, which includes nothing of the render kernels.
+// The HIP check and the flag mapping are launch_common.h's.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -14,15 +15,9 @@
 #include "comm.h"
 #include "accum_state.h"
 #include "denoise_kernels.h"
+#include "launch_common.h"
 
 using namespace rt;
-
-#define HIPCHK(expr)                                                                    \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess)                                                               \
-      return set_error(RT_E_HIP, std::string(#expr " failed: ") + hipGetErrorString(e_)); \
-  } while (0)
 
 // The argument checks of the run entries read nothing of this struct: tests hand them a zeroed host-made one.
 struct rt_denoise {
@@ -72,7 +67,7 @@ int build_guides(rt_denoise* d, hipStream_t st, const std::string& w) {
     std::memset(&tp, 0, sizeof(tp));
     tp.seed = a->rp.seed;
     tp.first_key = 0;
-    tp.flags = ((a->rp.flags & RT_RENDER_GENERIC) ? RT_TRACE_GENERIC : 0u) | ((a->rp.flags & RT_RENDER_NOCULL) ? RT_TRACE_NOCULL : 0u);
+    tp.flags = trace_flags_of(a->rp.flags);
     rc = rt_camera_rays_device(s, &q, 0, rays, st);
     if (rc == RT_OK) rc = rt_trace_rays_device(s, &tp, rays, n, hits, nullptr, st);
     if (rc != RT_OK) rc = set_error(rc, w + ": " + rt_last_error());

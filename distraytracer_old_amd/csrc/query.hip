@@ -2,6 +2,7 @@
 // occlusion of the caller's rays. The kernels (query_kernels.h) are the render kernels' traversal
 // code without shading, instantiated here, in a translation unit of their own, so that the render
 // kernels' register allocation in trace.hip / render_minreg.hip is not disturbed.
+// The host plumbing shared with the other units (HIP check, variant lookup, staging) is launch_common.h's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,23 +14,16 @@
 #define RT_MINREG_TU
 #include "rt_internal.h"
 #include "query_kernels.h"
+#include "launch_common.h"
 
 using namespace rt;
-
-#define HIPCHK(expr)                                                                    \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess)                                                               \
-      return set_error(RT_E_HIP, std::string(#expr " failed: ") + hipGetErrorString(e_)); \
-  } while (0)
 
 static_assert(sizeof(rt_ray) == 56 && sizeof(rt_hit) == 80 && sizeof(rt_trace_params) == 24, "ABI layout");
 
 namespace {
 
-constexpr uint32_t F_C4 = dv::FT_PRIM | dv::FT_TRANS | dv::FT_TEX | dv::FT_LIGHTX;
-// the kernels never reach the noise textures (no shading), so the per-translation-unit Perlin
-// tables (trace_kernels.h c_perm / c_grad3), which only trace.hip uploads, are not read here
+// the kernels never reach the noise textures (no shading), so this unit uploads no copy of the
+// per-translation-unit Perlin tables (trace_kernels.h c_perm / c_grad3; launch_common.h perlin_ready)
 
 typedef void (*QueryFn)(SceneD, uint64_t, uint64_t, const rt_ray*, int64_t, rt_hit*, uint8_t*);
 struct QueryVariant {
@@ -44,17 +38,10 @@ struct QueryVariant {
       }                                                                                            \
     }                                                                                              \
   }
-// the masks of the render's counting variants (trace.hip kCountVariants): a query walks the
-// specialised traversal the scene's render runs where one matches exactly, else the generic one
-const QueryVariant kQueryVariants[] = {QV(0u), QV(F_C4), QV(dv::F_C5), QV((uint32_t)dv::FT_ALL)};
+// a query walks the specialised traversal the scene's render runs where one matches exactly, else the generic
+// one (launch_common.h variant_for)
+const QueryVariant kQueryVariants[] = {RT_VARIANT_MASKS(QV)};
 #undef QV
-
-const QueryVariant& query_variant(const rt_scene* s, uint32_t flags) {
-  const uint32_t m = render_variant_mask(s, (flags & RT_TRACE_GENERIC) ? RT_RENDER_GENERIC : 0u);
-  for (const QueryVariant& v : kQueryVariants)
-    if (v.mask == m) return v;
-  return kQueryVariants[sizeof(kQueryVariants) / sizeof(kQueryVariants[0]) - 1];
-}
 
 // arguments checked before the scene is read or any device call is made
 int check_args(const char* who, const rt_scene* s, const rt_trace_params* p, const rt_ray* rays, int64_t n, const rt_hit* hits,
@@ -86,9 +73,10 @@ int check_order_args(const char* who, const rt_scene* s, const rt_trace_params* 
 int launch_query(rt_scene* s, uint32_t flags, uint64_t seed, uint64_t firstKey, const rt_ray* d_rays, int64_t n, rt_hit* d_hits,
                  uint8_t* d_occ, hipStream_t st) {
   if (flags & RT_TRACE_SORT) return sorted_query(s, flags, seed, firstKey, d_rays, n, d_hits, d_occ, st);
-  const SceneD sd = render_scene_view(s, (flags & RT_TRACE_NOCULL) ? RT_RENDER_NOCULL : 0u);
+  const SceneD sd = render_scene_view(s, render_flags_of(flags));
   const bool any = (flags & RT_TRACE_ANY) != 0;
-  const QueryFn fn = query_variant(s, flags).fn[(flags & RT_TRACE_LANES) ? 1 : 0][any ? 1 : 0];
+  const QueryVariant& v = variant_for(kQueryVariants, render_variant_mask(s, render_flags_of(flags)));
+  const QueryFn fn = v.fn[(flags & RT_TRACE_LANES) ? 1 : 0][any ? 1 : 0];
   constexpr int64_t SLICE = (int64_t)1 << 30;  // rays per launch: 2^24 blocks
   for (int64_t at = 0; at < n; at += SLICE) {
     const int64_t m = std::min(SLICE, n - at);
@@ -98,8 +86,6 @@ int launch_query(rt_scene* s, uint32_t flags, uint64_t seed, uint64_t firstKey, 
   }
   return RT_OK;
 }
-
-constexpr size_t RAY_B = sizeof(rt_ray), HIT_B = sizeof(rt_hit);
 
 void stage_free(rt_scene* s) {
   (void)hipFree(s->traceDev);
@@ -120,30 +106,6 @@ int order_windows(rt_scene* s, const rt_ray* d_rays, int64_t n, uint32_t* d_orde
   return RT_OK;
 }
 
-
-// the scene's stream and its staging buffers for min(n, chunk) rays: [cap rays][cap hits][cap bytes] on the
-// device and pinned on the host (grow-only)
-int stage_ready(rt_scene* s, int64_t n, hipStream_t* out) {
-  HIPCHK(hipSetDevice(s->device));
-  if (!s->stream) {
-    hipStream_t st;
-    HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    s->stream = st;
-  }
-  hipStream_t st = (hipStream_t)s->stream;
-  const size_t cap = (size_t)std::min<int64_t>(n, s->traceChunk);
-  if (cap > s->traceCap) {
-    HIPCHK(hipStreamSynchronize(st));
-    stage_free(s);
-    const size_t bytes = cap * (RAY_B + HIT_B + 1);
-    HIPCHK(hipMalloc(&s->traceDev, bytes));
-    HIPCHK(hipHostMalloc(&s->traceStage, bytes, hipHostMallocDefault));
-    s->traceCap = cap;
-  }
-  *out = st;
-  return RT_OK;
-}
-
 }  // namespace
 
 void rt::trace_init(rt_scene* s) {
@@ -160,11 +122,24 @@ void rt::trace_init(rt_scene* s) {
   if (const char* e = std::getenv("DISTRAYTRACER_SORT_DIR_BITS")) s->sortDirBits = std::min(16, std::max(1, std::atoi(e)));
 }
 
+// the scene's stream and its staging buffers for min(n, chunk) rays: [cap rays][cap hits][cap bytes] on the
+// device and pinned on the host (grow-only)
 int rt::trace_stage(rt_scene* s, int64_t n, void** stream) {
-  hipStream_t st = nullptr;
-  const int rc = stage_ready(s, n, &st);
+  HIPCHK(hipSetDevice(s->device));
+  hipStream_t st;
+  const int rc = scene_stream(s, &st);
+  if (rc != RT_OK) return rc;
+  const size_t cap = (size_t)std::min<int64_t>(n, s->traceChunk);
+  if (cap > s->traceCap) {
+    HIPCHK(hipStreamSynchronize(st));
+    stage_free(s);
+    const size_t bytes = cap * (sizeof(rt_ray) + sizeof(rt_hit) + 1);
+    HIPCHK(hipMalloc(&s->traceDev, bytes));
+    HIPCHK(hipHostMalloc(&s->traceStage, bytes, hipHostMallocDefault));
+    s->traceCap = cap;
+  }
   *stream = st;
-  return rc;
+  return RT_OK;
 }
 
 void rt::trace_free(rt_scene* s) {
@@ -191,58 +166,41 @@ int rt_trace_order_device(rt_scene* s, const rt_trace_params* p, const rt_ray* d
 }
 
 int rt_trace_order(rt_scene* s, const rt_trace_params* p, const rt_ray* rays, int64_t n, uint32_t* order) {
-  int rc = check_order_args("rt_trace_order", s, p, rays, n, order);
+  const int rc = check_order_args("rt_trace_order", s, p, rays, n, order);
   if (rc || n == 0) return rc;
-  hipStream_t st;
-  if ((rc = stage_ready(s, n, &st)) != RT_OK) return rc;
-  const size_t C = s->traceCap;
-  char *dev = (char*)s->traceDev, *stg = (char*)s->traceStage;
-  rt_ray* dRays = (rt_ray*)dev;
-  uint32_t* dOrder = (uint32_t*)(dev + C * RAY_B);  // the chunk's hits buffer
-  const uint32_t* sOut = (const uint32_t*)(stg + C * RAY_B);
-  for (int64_t at = 0; at < n; at += s->traceChunk) {  // each staging chunk is sorted on its own
-    const size_t m = (size_t)std::min<int64_t>(s->traceChunk, n - at);
-    std::memcpy(stg, rays + at, m * RAY_B);
-    hipError_t e = hipMemcpyAsync(dRays, stg, m * RAY_B, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) rc = order_windows(s, dRays, (int64_t)m, dOrder, st);
-    if (e == hipSuccess && rc == RT_OK) e = hipMemcpyAsync((void*)sOut, dOrder, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
-    const hipError_t se = hipStreamSynchronize(st);
-    if (rc != RT_OK) return rc;
-    if (e != hipSuccess) return set_error(RT_E_HIP, std::string("rt_trace_order: ") + hipGetErrorString(e));
-    if (se != hipSuccess) return set_error(RT_E_HIP, std::string("rt_trace_order kernel: ") + hipGetErrorString(se));
-    for (size_t i = 0; i < m; i++) order[at + (int64_t)i] = sOut[i] + (uint32_t)at;  // chunk-relative -> caller index
-  }
-  return RT_OK;
+  return staged_chunks(  // each staging chunk is sorted on its own, its order in the chunk's hit slots
+      "rt_trace_order", s, n,
+      [&](const Staging& g, int64_t at, size_t m, hipStream_t st) {
+        Enqueued q = {RT_OK, g.upload(rays + at, m, st)};
+        if (q.e == hipSuccess) q.rc = order_windows(s, g.dev.rays, (int64_t)m, (uint32_t*)g.dev.hits, st);
+        if (q.e == hipSuccess && q.rc == RT_OK) q.e = hipMemcpyAsync(g.pin.hits, g.dev.hits, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+        return q;
+      },
+      [&](const Staging& g, int64_t at, size_t m) {
+        const uint32_t* sOut = (const uint32_t*)g.pin.hits;
+        for (size_t i = 0; i < m; i++) order[at + (int64_t)i] = sOut[i] + (uint32_t)at;  // chunk-relative -> caller index
+      });
 }
 
 int rt_trace_rays(rt_scene* s, const rt_trace_params* p, const rt_ray* rays, int64_t n, rt_hit* hits, uint8_t* occluded) {
-  int rc = check_args("rt_trace_rays", s, p, rays, n, hits, occluded);
+  const int rc = check_args("rt_trace_rays", s, p, rays, n, hits, occluded);
   if (rc || n == 0) return rc;
-  hipStream_t st;
-  if ((rc = stage_ready(s, n, &st)) != RT_OK) return rc;
-  const bool any = (p->flags & RT_TRACE_ANY) != 0;
-  const size_t C = s->traceCap;
-  char *dev = (char*)s->traceDev, *stg = (char*)s->traceStage;
-  rt_ray* dRays = (rt_ray*)dev;
-  rt_hit* dHits = (rt_hit*)(dev + C * RAY_B);
-  uint8_t* dOcc = (uint8_t*)(dev + C * (RAY_B + HIT_B));
-  char* sOut = stg + C * RAY_B;  // hits or occlusion bytes of the chunk
-  for (int64_t at = 0; at < n; at += s->traceChunk) {
-    const size_t m = (size_t)std::min<int64_t>(s->traceChunk, n - at);
-    const size_t outB = any ? m : m * HIT_B;
-    std::memcpy(stg, rays + at, m * RAY_B);
-    hipError_t e = hipMemcpyAsync(dRays, stg, m * RAY_B, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) rc = launch_query(s, p->flags, p->seed, p->first_key + (uint64_t)at, dRays, (int64_t)m, dHits, dOcc, st);
-    if (e == hipSuccess && rc == RT_OK)
-      e = hipMemcpyAsync(sOut, any ? (const void*)dOcc : (const void*)dHits, outB, hipMemcpyDeviceToHost, st);
-    const hipError_t se = hipStreamSynchronize(st);  // the call blocks until the chunk is in the staging buffer
-    if (rc != RT_OK) return rc;
-    if (e != hipSuccess) return set_error(RT_E_HIP, std::string("rt_trace_rays: ") + hipGetErrorString(e));
-    if (se != hipSuccess) return set_error(RT_E_HIP, std::string("rt_trace_rays kernel: ") + hipGetErrorString(se));
-    if (any) std::memcpy(occluded + at, sOut, outB);
-    else std::memcpy(hits + at, sOut, outB);
-  }
-  return RT_OK;
+  const bool any = (p->flags & RT_TRACE_ANY) != 0;  // the chunk's occlusion bytes come back in the pinned hit slots
+  return staged_chunks(
+      "rt_trace_rays", s, n,
+      [&](const Staging& g, int64_t at, size_t m, hipStream_t st) {
+        Enqueued q = {RT_OK, g.upload(rays + at, m, st)};
+        if (q.e == hipSuccess)
+          q.rc = launch_query(s, p->flags, p->seed, p->first_key + (uint64_t)at, g.dev.rays, (int64_t)m, g.dev.hits, g.dev.bytes, st);
+        if (q.e == hipSuccess && q.rc == RT_OK)
+          q.e = hipMemcpyAsync(g.pin.hits, any ? (const void*)g.dev.bytes : (const void*)g.dev.hits, any ? m : m * sizeof(rt_hit),
+                               hipMemcpyDeviceToHost, st);
+        return q;
+      },
+      [&](const Staging& g, int64_t at, size_t m) {
+        if (any) std::memcpy(occluded + at, g.pin.hits, m);
+        else std::memcpy(hits + at, g.pin.hits, m * sizeof(rt_hit));
+      });
 }
 
 }  // extern "C"

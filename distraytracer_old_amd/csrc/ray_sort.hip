@@ -5,6 +5,7 @@
 // query_kernel_idx). The indices are sorted iota values: a permutation whatever the keys are. The
 // indexed instantiations of the heavy kernels live here, so that query.hip's are not disturbed and the
 // two translation units compile in parallel.
+// The host plumbing shared with the other units (HIP check, variant lookup, staging) is launch_common.h's.
 #include <hip/hip_runtime.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -17,15 +18,9 @@
 #define RT_MINREG_TU
 #include "rt_internal.h"
 #include "query_kernels.h"
+#include "launch_common.h"
 
 using namespace rt;
-
-#define HIPCHK(expr)                                                                    \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess)                                                               \
-      return set_error(RT_E_HIP, std::string(#expr " failed: ") + hipGetErrorString(e_)); \
-  } while (0)
 
 namespace {
 
@@ -134,7 +129,6 @@ __global__ void __launch_bounds__(256) key_kernel(const rt_ray* __restrict__ ray
 }
 
 // ---- the indexed query kernels ------------------------------------------------------------------------
-constexpr uint32_t F_C4 = dv::FT_PRIM | dv::FT_TRANS | dv::FT_TEX | dv::FT_LIGHTX;
 typedef void (*QueryIdxFn)(SceneD, uint64_t, uint64_t, const rt_ray*, int64_t, rt_hit*, uint8_t*, const uint32_t*);
 struct QueryIdxVariant {
   uint32_t mask;
@@ -148,16 +142,8 @@ struct QueryIdxVariant {
       }                                                                                            \
     }                                                                                              \
   }
-// the masks of query.hip's kQueryVariants, picked by the same rule
-const QueryIdxVariant kQueryIdxVariants[] = {QV(0u), QV(F_C4), QV(dv::F_C5), QV((uint32_t)dv::FT_ALL)};
+const QueryIdxVariant kQueryIdxVariants[] = {RT_VARIANT_MASKS(QV)};
 #undef QV
-
-const QueryIdxVariant& query_idx_variant(const rt_scene* s, uint32_t flags) {
-  const uint32_t m = render_variant_mask(s, (flags & RT_TRACE_GENERIC) ? RT_RENDER_GENERIC : 0u);
-  for (const QueryIdxVariant& v : kQueryIdxVariants)
-    if (v.mask == m) return v;
-  return kQueryIdxVariants[sizeof(kQueryIdxVariants) / sizeof(kQueryIdxVariants[0]) - 1];
-}
 
 // scratch layout for a capacity of C rays: keys[2][C] (8 B), idx[2][C] (4 B), the bounds cell, the temporary storage
 constexpr size_t CELL_B = 64;
@@ -214,9 +200,10 @@ int rt::sort_order(rt_scene* s, const rt_ray* d_rays, int64_t n, uint32_t base, 
 int rt::sorted_query(rt_scene* s, uint32_t flags, uint64_t seed, uint64_t firstKey, const rt_ray* d_rays, int64_t n, rt_hit* d_hits,
                      uint8_t* d_occ, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  const SceneD sd = render_scene_view(s, (flags & RT_TRACE_NOCULL) ? RT_RENDER_NOCULL : 0u);
+  const SceneD sd = render_scene_view(s, render_flags_of(flags));
   const bool any = (flags & RT_TRACE_ANY) != 0;
-  const QueryIdxFn fn = query_idx_variant(s, flags).fn[(flags & RT_TRACE_LANES) ? 1 : 0][any ? 1 : 0];
+  const QueryIdxVariant& v = variant_for(kQueryIdxVariants, render_variant_mask(s, render_flags_of(flags)));
+  const QueryIdxFn fn = v.fn[(flags & RT_TRACE_LANES) ? 1 : 0][any ? 1 : 0];
   // windows are independent: indices, keys and records are relative to the window's first ray
   for (int64_t at = 0; at < n; at += s->sortWindow) {
     const int64_t m = std::min(s->sortWindow, n - at);

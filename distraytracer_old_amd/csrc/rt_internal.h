@@ -91,8 +91,9 @@ int check_photon_params(const HostScene& h);
 int shoot_photons(rt_scene* s, uint64_t seed, int64_t first, int64_t count, std::vector<double>& pos,
                   std::vector<double>& pwr, std::vector<int64_t>& perLight);
 int set_photon_map(rt_scene* s, std::vector<double>& pos, std::vector<double>& pwr);
-// trace.hip, for query.hip's ray queries: the feature mask of the render variant a scene runs and
-// the scene view of a launch (both as rt_render's, by the RT_RENDER_* flags)
+// trace.hip, for every unit that launches kernels of its own on a scene (query, ray_sort, shade, accum,
+// adaptive): the feature mask of the render variant the scene runs, by which launch_common.h's variant_for
+// picks that unit's kernel, and the scene view of a launch (both as rt_render's, by the RT_RENDER_* flags)
 uint32_t render_variant_mask(const rt_scene* s, uint32_t render_flags);
 SceneD render_scene_view(const rt_scene* s, uint32_t render_flags);
 // query.hip: the chunk size of rt_trace_rays (scene creation), its buffers freed (rt_scene_destroy)
@@ -107,11 +108,12 @@ int sort_order(rt_scene* s, const rt_ray* d_rays, int64_t n, uint32_t base, cons
 int sorted_query(rt_scene* s, uint32_t flags, uint64_t seed, uint64_t firstKey, const rt_ray* d_rays, int64_t n, rt_hit* d_hits,
                  uint8_t* d_occ, void* stream);
 void sort_free(rt_scene* s);
-// shade.hip (rt_shade_rays, rt_camera_rays) borrows two things. query.hip: the scene's stream (hipStream_t
-// in *stream) and rt_trace_rays' staging grown to min(n, traceChunk) rays -- [cap rays][cap hits][cap bytes]
-// on the device (traceDev) and pinned on the host (traceStage), cap = traceCap. trace.hip: the host copies of
-// the Perlin tables (256 and 12 x 3 ints), which every translation unit that reaches the noise textures
-// uploads into its own c_perm / c_grad3.
+// query.hip, for the host-buffer entries of any unit (launch_common.h staged_chunks: rt_trace_rays,
+// rt_trace_order, rt_shade_rays, rt_camera_rays): the scene's stream (hipStream_t in *stream) and the staging
+// grown to min(n, traceChunk) rays -- [cap rays][cap hits][cap bytes] on the device (traceDev) and pinned on the
+// host (traceStage), cap = traceCap; launch_common.h's Staging hands out the typed pointers.
+// trace.hip: the host copies of the Perlin tables (256 and 12 x 3 ints), which every translation unit that
+// reaches the noise textures uploads into its own c_perm / c_grad3 (launch_common.h perlin_ready).
 int trace_stage(rt_scene* s, int64_t n, void** stream);
 void perlin_tables(const int** perm, const int** grad3);
 // group.hip: the deterministic rank plan (rt_rank_plan)
@@ -130,8 +132,9 @@ struct rt_scene {
   bool photonsUploaded = false;
   void* counters = nullptr;  // device uint64[RT_ST_N]
   // rt_render / rt_render_count (host buffers): output buffers kept across calls (grow-only)
-  // and the scene's own non-blocking stream, so the blocking per-frame entry (the JNI
-  // nativeRender path) pays no hipMalloc / hipFree / device-wide synchronisation per call
+  // and the scene's own non-blocking stream (launch_common.h scene_stream creates it on first use), so the
+  // blocking per-frame entry (the JNI nativeRender path) pays no hipMalloc / hipFree / device-wide
+  // synchronisation per call
   float* outRgb = nullptr;
   int32_t* outArgb = nullptr;
   size_t outCap = 0;  // pixels
@@ -164,8 +167,9 @@ struct rt_scene {
   void* smpTr = nullptr;
   size_t smpCap = 0;  // samples
   size_t wfCap[WF_N] = {};
-  // rt_trace_rays (query.hip): device rays / hits / occlusion bytes of one chunk and their pinned
-  // staging (grow-only), and the chunk size in rays (DISTRAYTRACER_TRACE_CHUNK, read at creation)
+  // the host-buffer ray entries (query.hip trace_stage, launch_common.h Staging): device rays / hits / bytes of
+  // one chunk and their pinned staging (grow-only), and the chunk size in rays (DISTRAYTRACER_TRACE_CHUNK, read
+  // at creation)
   void* traceDev = nullptr;
   void* traceStage = nullptr;
   size_t traceCap = 0;  // rays

@@ -1,6 +1,6 @@
 // C-ABI render entry points (include/distraytracer.h): scene upload, kernel
 // variant dispatch, launches and the photon pre-pass driver. The kernels are in
-// trace_kernels.h.
+// trace_kernels.h, the host plumbing shared with the other units in launch_common.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,6 +14,7 @@
 #include "rt_internal.h"
 #include "trace_kernels.h"
 #include "wavefront.h"
+#include "launch_common.h"
 // ===========================================================================
 // host side: device upload + C ABI
 using namespace rt;
@@ -23,13 +24,6 @@ int rt::set_error(int code, const std::string& msg) {
   g_last_error = msg;
   return code;
 }
-
-#define HIPCHK(expr)                                                                    \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess)                                                               \
-      return set_error(RT_E_HIP, std::string(#expr " failed: ") + hipGetErrorString(e_)); \
-  } while (0)
 
 static const int H_PERM[256] = {151,160,137,91,90,15,131,13,201,95,96,53,194,233,7,225,140,36,103,30,69,142,8,99,37,240,21,10,23,
   190,6,148,247,120,234,75,0,26,197,62,94,252,219,203,117,35,11,32,57,177,33,88,237,149,56,87,174,20,125,136,171,168,68,175,74,165,71,
@@ -587,39 +581,18 @@ struct Variant {
   RenderFn fn;
 };
 // smallest first; the first variant whose mask covers the scene's features runs
+#define RV(F) {F, dv::render_kernel<false, F>}
 static const Variant kVariants[] = {
-    {0u, dv::render_kernel<false, 0u>},
-    {dv::FT_PRIM, dv::render_kernel<false, dv::FT_PRIM>},
-    {dv::FT_PRIM | dv::FT_TRANS | dv::FT_TEX | dv::FT_LIGHTX,
-     dv::render_kernel<false, dv::FT_PRIM | dv::FT_TRANS | dv::FT_TEX | dv::FT_LIGHTX>},
-    {dv::FT_PRIM | dv::FT_TRANS | dv::FT_PHOTON | dv::FT_LIGHTX,
-     dv::render_kernel<false, dv::FT_PRIM | dv::FT_TRANS | dv::FT_PHOTON | dv::FT_LIGHTX>},
-    {dv::FT_PRIM | dv::FT_INST | dv::FT_TRANS | dv::FT_TEX | dv::FT_LIGHTX,
-     dv::render_kernel<false, dv::FT_PRIM | dv::FT_INST | dv::FT_TRANS | dv::FT_TEX | dv::FT_LIGHTX>},
-    {dv::FT_ALL, dv::render_kernel<false, dv::FT_ALL>},
+    RV(0u), RV(dv::FT_PRIM), RV(dv::F_C4), RV(dv::F_C5), RV(dv::F_C4 | dv::FT_INST), RV((uint32_t)dv::FT_ALL),
 };
+#undef RV
 
 // RT_RENDER_SHCOMPACT: the same variants with the wave's shadow rays traced compacted
 // (render_kernel<..., true>); the ones the benchmark configs run, and the generic one
-static const Variant kVariantsShc[] = {
-    {0u, dv::render_kernel<false, 0u, true>},
-    {dv::FT_PRIM | dv::FT_TRANS | dv::FT_TEX | dv::FT_LIGHTX,
-     dv::render_kernel<false, dv::FT_PRIM | dv::FT_TRANS | dv::FT_TEX | dv::FT_LIGHTX, true>},
-    {dv::FT_PRIM | dv::FT_TRANS | dv::FT_PHOTON | dv::FT_LIGHTX,
-     dv::render_kernel<false, dv::FT_PRIM | dv::FT_TRANS | dv::FT_PHOTON | dv::FT_LIGHTX, true>},
-    {dv::FT_ALL, dv::render_kernel<false, dv::FT_ALL, true>},
-};
+#define RV(F) {F, dv::render_kernel<false, F, true>}
+static const Variant kVariantsShc[] = {RT_VARIANT_MASKS(RV)};
+#undef RV
 
-static RenderFn pick_variant(const HostScene& h, uint32_t flags) {
-  uint32_t f = (flags & RT_RENDER_GENERIC) ? (uint32_t)dv::FT_ALL : scene_features(h);
-  if (flags & RT_RENDER_SHCOMPACT) {
-    for (const Variant& v : kVariantsShc)
-      if ((f & ~v.mask) == 0) return v.fn;
-  }
-  for (const Variant& v : kVariants)
-    if ((f & ~v.mask) == 0) return v.fn;
-  return dv::render_kernel<false, dv::FT_ALL>;
-}
 // the feature mask of the variant pick_variant launches (without RT_RENDER_SHCOMPACT)
 static uint32_t variant_mask(const HostScene& h, uint32_t flags) {
   const uint32_t f = (flags & RT_RENDER_GENERIC) ? (uint32_t)dv::FT_ALL : scene_features(h);
@@ -627,23 +600,24 @@ static uint32_t variant_mask(const HostScene& h, uint32_t flags) {
     if ((f & ~v.mask) == 0) return v.mask;
   return dv::FT_ALL;
 }
+static RenderFn pick_variant(const HostScene& h, uint32_t flags) {
+  if (flags & RT_RENDER_SHCOMPACT) {
+    const uint32_t f = (flags & RT_RENDER_GENERIC) ? (uint32_t)dv::FT_ALL : scene_features(h);
+    for (const Variant& v : kVariantsShc)  // its last entry covers every scene
+      if ((f & ~v.mask) == 0) return v.fn;
+  }
+  return variant_for(kVariants, variant_mask(h, flags)).fn;
+}
 
 // Instrumented (counting) instantiations of the timed variants the benchmark configs run -- C3's
 // (triangles only: nearest-first BVH traversal compiled in), C4's and C5's -- so the counted record
 // loads are the ones the timed kernel issues (bench.py's roofline numerator); other scenes count
 // with the all-features kernel.
-static const Variant kCountVariants[] = {
-    {0u, dv::render_kernel<true, 0u>},
-    {dv::FT_PRIM | dv::FT_TRANS | dv::FT_TEX | dv::FT_LIGHTX,
-     dv::render_kernel<true, dv::FT_PRIM | dv::FT_TRANS | dv::FT_TEX | dv::FT_LIGHTX>},
-    {dv::F_C5, dv::render_kernel<true, dv::F_C5>},
-    {dv::FT_ALL, dv::render_kernel<true, dv::FT_ALL>},
-};
+#define RV(F) {F, dv::render_kernel<true, F>}
+static const Variant kCountVariants[] = {RT_VARIANT_MASKS(RV)};
+#undef RV
 static const Variant& count_variant(const HostScene& h, uint32_t flags) {
-  const uint32_t m = (flags & RT_RENDER_SHCOMPACT) ? (uint32_t)dv::FT_ALL : variant_mask(h, flags);
-  for (const Variant& v : kCountVariants)
-    if (v.mask == m) return v;
-  return kCountVariants[sizeof(kCountVariants) / sizeof(kCountVariants[0]) - 1];
+  return variant_for(kCountVariants, (flags & RT_RENDER_SHCOMPACT) ? (uint32_t)dv::FT_ALL : variant_mask(h, flags));
 }
 
 // Dispatch schedule: tiles sorted by cost, longest first, so the long tiles do not end
@@ -818,9 +792,8 @@ static int render_wf(rt_scene* s, const SceneD& sd, const ParamsD& P, float* d_r
 static int render_wavefront(rt_scene* s, const SceneD& sd, const ParamsD& P, uint32_t flags, float* d_rgb, int32_t* d_argb,
                             hipStream_t st) {
   const uint32_t f = (flags & RT_RENDER_GENERIC) ? (uint32_t)dv::FT_ALL : scene_features(s->hs);
-  constexpr uint32_t C4 = dv::FT_PRIM | dv::FT_TRANS | dv::FT_TEX | dv::FT_LIGHTX;
   if (f == 0) return render_wf<0u>(s, sd, P, d_rgb, d_argb, st);
-  if ((f & ~C4) == 0) return render_wf<C4>(s, sd, P, d_rgb, d_argb, st);
+  if ((f & ~dv::F_C4) == 0) return render_wf<dv::F_C4>(s, sd, P, d_rgb, d_argb, st);
   return render_wf<dv::FT_ALL>(s, sd, P, d_rgb, d_argb, st);
 }
 
@@ -890,12 +863,8 @@ static int render_host(rt_scene* s, const rt_render_params* p, float* rgb, int32
   int rc = make_params(s, p, P);
   if (rc) return rc;
   HIPCHK(hipSetDevice(s->device));
-  if (!s->stream) {
-    hipStream_t st;
-    HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    s->stream = st;
-  }
-  hipStream_t st = (hipStream_t)s->stream;
+  hipStream_t st;
+  if ((rc = scene_stream(s, &st)) != RT_OK) return rc;
   const size_t npx = (size_t)P.nrows * P.W;
   if (npx > s->outCap) {  // grow-only device output buffers, reused by later calls
     HIPCHK(hipStreamSynchronize(st));
@@ -924,9 +893,7 @@ static int render_host(rt_scene* s, const rt_render_params* p, float* rgb, int32
   if (rc == RT_OK && e == hipSuccess && argb) e = hipMemcpyAsync(stg + nrgb, s->outArgb, npx * sizeof(int32_t), hipMemcpyDeviceToHost, st);
   if (rc == RT_OK && e == hipSuccess && stats)
     e = hipMemcpyAsync(stats, s->counters, sizeof(uint64_t) * RT_ST_N, hipMemcpyDeviceToHost, st);
-  hipError_t se = hipStreamSynchronize(st);  // the call blocks until the frame is in the caller's buffers
-  if (rc == RT_OK && e != hipSuccess) rc = set_error(RT_E_HIP, hipGetErrorString(e));
-  if (rc == RT_OK && se != hipSuccess) rc = set_error(RT_E_HIP, std::string("render kernel: ") + hipGetErrorString(se));
+  rc = sync_report(st, rc, e, "", "render kernel: ");  // the call blocks until the frame is in the caller's buffers
   if (rc == RT_OK && rgb) std::memcpy(rgb, stg, nrgb);
   if (rc == RT_OK && argb) std::memcpy(argb, stg + nrgb, npx * sizeof(int32_t));
   return rc;
@@ -1108,12 +1075,8 @@ int rt_render_tiles_count(rt_scene* s, const rt_render_params* p, const int32_t*
   const int32_t* dt = nullptr;
   rc = tile_list(s, P, tiles, ntiles, &dt);
   if (rc) return rc;
-  if (!s->stream) {
-    hipStream_t st;
-    HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    s->stream = st;
-  }
-  hipStream_t st = (hipStream_t)s->stream;
+  hipStream_t st;
+  if ((rc = scene_stream(s, &st)) != RT_OK) return rc;
   const size_t npx = (size_t)P.nrows * P.W;
   float* d_rgb = nullptr;
   int32_t* d_argb = nullptr;
@@ -1121,11 +1084,9 @@ int rt_render_tiles_count(rt_scene* s, const rt_render_params* p, const int32_t*
   hipError_t e = hipMalloc(&d_argb, npx * sizeof(int32_t));
   if (e == hipSuccess) rc = launch(s, P, p->flags, d_rgb, d_argb, true, st, dt, ntiles);
   if (e == hipSuccess && rc == RT_OK) e = hipMemcpyAsync(stats, s->counters, sizeof(uint64_t) * RT_ST_N, hipMemcpyDeviceToHost, st);
-  hipError_t se = hipStreamSynchronize(st);
+  rc = sync_report(st, rc, e, "", "count kernel: ");
   (void)hipFree(d_rgb);
   (void)hipFree(d_argb);
-  if (rc == RT_OK && e != hipSuccess) rc = set_error(RT_E_HIP, hipGetErrorString(e));
-  if (rc == RT_OK && se != hipSuccess) rc = set_error(RT_E_HIP, std::string("count kernel: ") + hipGetErrorString(se));
   return rc;
 }
 
@@ -1149,10 +1110,9 @@ static int pixel_samples(rt_scene* s, const ParamsD& P, uint32_t flags, const in
                          uint8_t* smpTr, float* d_rgb, int32_t* d_argb, hipStream_t st) {
   const SceneD sd = launch_scene(s, flags);
   const uint32_t f = (flags & RT_RENDER_GENERIC) ? (uint32_t)dv::FT_ALL : scene_features(s->hs);
-  constexpr uint32_t C4 = dv::FT_PRIM | dv::FT_TRANS | dv::FT_TEX | dv::FT_LIGHTX;
   if (f == 0) return launch_pixels<0u>(sd, P, dpix, npix, smpCol, smpTr, d_rgb, d_argb, st);
   if ((f & ~dv::F_C5) == 0) return launch_pixels<dv::F_C5>(sd, P, dpix, npix, smpCol, smpTr, d_rgb, d_argb, st);
-  if ((f & ~C4) == 0) return launch_pixels<C4>(sd, P, dpix, npix, smpCol, smpTr, d_rgb, d_argb, st);
+  if ((f & ~dv::F_C4) == 0) return launch_pixels<dv::F_C4>(sd, P, dpix, npix, smpCol, smpTr, d_rgb, d_argb, st);
   return launch_pixels<dv::FT_ALL>(sd, P, dpix, npix, smpCol, smpTr, d_rgb, d_argb, st);
 }
 

@@ -3591,6 +3591,7 @@ __device__ unsigned long long* rt_tl_buf;
 #else
 #define RT_SPLIT_TU 1
 #endif
+static constexpr uint32_t F_C4 = FT_PRIM | FT_TRANS | FT_TEX | FT_LIGHTX;
 static constexpr uint32_t F_C5 = FT_PRIM | FT_TRANS | FT_PHOTON | FT_LIGHTX;
 // SHC: the shading steps of a wave run in step and their shadow rays are traced compacted
 // (trace_sample_w / light_sum_w) instead of lane by lane (trace_sample)

@@ -6,7 +6,8 @@ Scene.shade folded in numpy for the raw sums, and an accumulator without counts 
    (list lengths that are no multiple of the wave's 64 / G entries), then one mask with a chunk of every G.
 2. The same on the feature scenes (BVH, transparency, disk light, textures, fisheye, lens, photon map).
 3. The raw sums equal the numpy fold of the shaded camera rays, taken to each pixel's own count.
-4. Chunk invariance; an all-pixels selection equals add(); RENDER_GENERIC / RENDER_NOCULL give the same bytes.
+4. Chunk invariance; an all-pixels selection equals add(), also as a procedural-noise scene's first shading;
+   RENDER_GENERIC / RENDER_NOCULL give the same bytes.
 5. The selection is the mask's pixels in the documented tile-major order, from a host or a device mask.
 6. select_error selects the numpy predicate's pixels; the error map of per-pixel counts equals its definition.
 7. Checkpoint with counts; reset. 8. A caller's stream. 9. The driver's -noise mode."""
@@ -239,6 +240,22 @@ def test_chunk_invariance_and_all_pixels(scene_of):
             assert (a.counts() == n).all() and a.samples == 0 and b.samples == n
             _same(a.state()[1], b.state()[1], ("all pixels against add", n, "sum"))
             _same(a.state()[2], b.state()[2], ("all pixels against add", n, "sq"))
+
+
+def test_procedural_noise_on_a_scene_that_has_not_rendered(scene_of):
+    """The selective add's kernels read their own translation unit's copy of the Perlin tables. On a scene with
+    procedural wood whose first shading is add_selected, an all-pixels selection equals the plain accumulator's add."""
+    cli, W, H, n = "p3_t09.cli", 32, 32, 2
+    g = scene_of(cli)  # no other test of this module opens it
+    every = np.ones((H, W), dtype=bool)
+    with g.accumulator(W, H, seed=SEED, moments=True, counts=True) as a, g.accumulator(W, H, seed=SEED, moments=True) as b:
+        assert a.select_mask(every) == W * H
+        a.add_selected(n)
+        b.add(n)
+        assert (a.counts() == n).all()
+        _same(a.state()[1], b.state()[1], (cli, "sum"))
+        _same(a.state()[2], b.state()[2], (cli, "sq"))
+        assert len(np.unique(a.state()[1])) > 16  # the frame shows something
 
 
 @pytest.mark.parametrize("cli", ["p2_t05.cli", "c3shinyBall.cli"])

@@ -28,7 +28,7 @@ LIB_PATH = LIB_DIR / "libdistraytracer.so"
 INFO_PATH = LIB_DIR / "libdistraytracer.buildinfo.json"
 PUBLIC_HEADER = PKG.parent / "include" / "distraytracer.h"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-SOURCES = ["trace.hip", "render_minreg.hip", "query.hip", "ray_sort.hip", "shade.hip", "accum.hip", "adaptive.hip", "denoise.hip", "photon_build.hip", "group.hip", "comm.hip", "cli_loader.cpp",
+SOURCES = ["trace.hip", "render_minreg.hip", "query.hip", "ray_sort.hip", "shade.hip", "accum.hip", "adaptive.hip", "pose.hip", "denoise.hip", "photon_build.hip", "group.hip", "comm.hip", "cli_loader.cpp",
            "scene_build.cpp", "photon.cpp", "build_id.cpp"]
 OBJ_DIR = LIB_DIR / "obj"
 # per-source compiler flags: render_minreg.hip holds C3's and C5's render variants, which run

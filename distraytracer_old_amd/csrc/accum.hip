@@ -25,6 +25,7 @@ namespace {
 constexpr uint32_t RENDER_FLAGS = RT_RENDER_GENERIC | RT_RENDER_NOCULL;
 constexpr uint32_t ACCUM_FLAGS = RT_ACCUM_MOMENTS | RT_ACCUM_COUNTS;
 
+// the kernels without a camera pose; an accumulator that has one launches pose.hip's (pose_launch_accum)
 typedef void (*AccumFn)(SceneD, ParamsD, int, double*, double*);
 struct AccumVariant {
   uint32_t mask;
@@ -184,12 +185,16 @@ int rt_accum_add(rt_accum* a, int count, void* hip_stream) {
     a->last = st;
     return RT_OK;
   }
-  const AccumVariant& v = variant_for(kAccumVariants, render_variant_mask(s, a->rp.flags));
   const int64_t tilesX = (P.W + P.tw - 1) / P.tw, tilesY = (P.H + P.th - 1) / P.th;
   if (tilesX * tilesY > INT32_MAX) return set_error(RT_E_INVALID, w + ": more than 2^31 - 1 tiles");
-  hipLaunchKernelGGL(v.fn[a->sq ? 1 : 0], dim3((unsigned)(tilesX * tilesY)), dim3(64), dv::LDS_RENDER_BYTES, st, sd, P, (int)a->done,
-                     a->sum, a->sq);
-  HIPCHK(hipGetLastError());
+  if (a->has_pose) {
+    if ((rc = pose_launch_accum(a, sd, P, (unsigned)(tilesX * tilesY), st)) != RT_OK) return rc;
+  } else {
+    const AccumVariant& v = variant_for(kAccumVariants, render_variant_mask(s, a->rp.flags));
+    hipLaunchKernelGGL(v.fn[a->sq ? 1 : 0], dim3((unsigned)(tilesX * tilesY)), dim3(64), dv::LDS_RENDER_BYTES, st, sd, P, (int)a->done,
+                       a->sum, a->sq);
+    HIPCHK(hipGetLastError());
+  }
   a->done += count;
   if (a->flags & RT_ACCUM_COUNTS) a->bound += count;
   a->last = st;
@@ -287,6 +292,31 @@ int rt_accum_reset(rt_accum* a) {
   if ((rc = zero_sums(a)) != RT_OK) return rc;
   a->done = 0;
   if (a->flags & RT_ACCUM_COUNTS) adaptive_uniform(a, 0);
+  return RT_OK;
+}
+
+int rt_accum_set_camera(rt_accum* a, const double* pose) {
+  const std::string w("rt_accum_set_camera");
+  if (!a) return set_error(RT_E_INVALID, w + ": null accumulator");
+  if (pose) {
+    const char* why = pose_invalid(pose);
+    if (why) return set_error(RT_E_INVALID, w + ": " + why);
+  }
+  const int rc = rt_accum_reset(a);  // the sums are of the old camera's rays
+  if (rc != RT_OK) return rc;
+  a->has_pose = pose ? 1 : 0;
+  if (pose) std::memcpy(a->pose, pose, sizeof(a->pose));
+  a->pose_gen += 1;
+  return RT_OK;
+}
+
+int rt_accum_camera(const rt_accum* a, double* pose, int* is_set) {
+  const std::string w("rt_accum_camera");
+  if (!a) return set_error(RT_E_INVALID, w + ": null accumulator");
+  if (!pose) return set_error(RT_E_INVALID, w + ": null pose");
+  if (!is_set) return set_error(RT_E_INVALID, w + ": null is_set");
+  for (int i = 0; i < 16; ++i) pose[i] = a->has_pose ? a->pose[i] : (i % 5 == 0 ? 1.0 : 0.0);
+  *is_set = a->has_pose;
   return RT_OK;
 }
 

@@ -30,9 +30,14 @@ namespace dv {
 // entered; they still run every round's two barriers, the loop bounds being wave-uniform. An untraced
 // sample adds nothing (the traced flag in cbuf's fourth slot; only the FT_CAMX masks can have one, the
 // others neither store nor test the flag) and is counted by the host in done: the render divides by spp.
-template <uint32_t F, bool MOM>
+//
+// POSE: the accumulator has a camera pose (rt_accum_set_camera). The last argument is then the PoseD, applied
+// to the ray between camera_ray and trace_sample (camera_ray.h pose_ray); the key does not change. Without
+// one the pack is empty, and the kernel is the code it was before there were poses.
+template <uint32_t F, bool MOM, bool POSE = false, class... M>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RT_RENDER_WAVES)))
-accum_kernel(SceneD S, ParamsD P, int done, double* __restrict__ sum, double* __restrict__ sq) {
+accum_kernel(SceneD S, ParamsD P, int done, double* __restrict__ sum, double* __restrict__ sq, M... pose) {
+  RT_POSE_PACK_CHECK(POSE, M);
   constexpr bool FLAG = (F & FT_CAMX) != 0;
   double* cbuf = rt_lds;  // 64 x 4 doubles (colour, traced)
   const int lane = threadIdx.x;
@@ -62,6 +67,7 @@ accum_kernel(SceneD S, ParamsD P, int done, double* __restrict__ sum, double* __
         V o, d;
         traced = camera_ray<F>(S, P, g.row, g.col, done + sl, true, o, d);
         if (traced) {
+          pose_ray(o, d, pose...);
           k.pixel = (uint64_t)g.row * (uint64_t)P.W + (uint64_t)g.col;
           k.sample = (uint32_t)(done + sl);
           Counters ct;
@@ -127,6 +133,7 @@ accum_kernel(SceneD S, ParamsD P, int done, double* __restrict__ sum, double* __
   }
 }
 
+#ifndef RT_POSE_TU  // the kernels defined outright: accum.hip only (pose.hip instantiates the posed accum_kernel)
 // the frame of n accumulated samples, one lane per pixel: render_kernel's epilogue on the carried sums --
 // clampc(sum / n), the float conversion and myColor.getInt's packing. rgb or argb may be null.
 __global__ void __launch_bounds__(256) resolve_kernel(const double* __restrict__ sum, int64_t npix, int64_t n,
@@ -168,6 +175,7 @@ __global__ void __launch_bounds__(256) error_kernel(const double* __restrict__ s
   }
   err[o] = (float)e;
 }
+#endif  // RT_POSE_TU
 
 }  // namespace dv
 }  // namespace rt

@@ -28,6 +28,10 @@ struct rt_accum {
   int32_t has_sel;    // a selection was made since creation, reset or restore
   int32_t mixed;      // a selective add or rt_accum_restore_counts made the counts differ from done
   int32_t all_ready;  // `all` is filled
+  // the camera pose (rt_accum_set_camera), behind everything older code reads
+  int32_t has_pose;   // 0: none -- every add runs the un-posed kernels
+  uint64_t pose_gen;  // counts the rt_accum_set_camera calls: a denoiser's guides are of one of them
+  double pose[16];    // row-major camera -> world, valid by rt_camera_pose_check (has_pose only)
 };
 
 // tests/test_accum_abi.py hands the entries a host-made accumulator with these two fields set: the refusals
@@ -44,5 +48,12 @@ void adaptive_uniform(rt_accum* a, int64_t n);    // every pixel has n samples a
 int adaptive_add_all(rt_accum* a, const rt::ParamsD& P, void* stream);  // rt_accum_add with mixed counts
 int adaptive_resolve(rt_accum* a, float* d_rgb, int32_t* d_argb, void* stream);
 int adaptive_error(rt_accum* a, float* d_err, void* stream);
+
+// pose.hip: accum.hip's and adaptive.hip's launches of an accumulator with a camera pose (a->has_pose): the
+// posed instantiations of accum_kernel and accum_list_kernel for the scene's variant, with the grid and the
+// arguments of the un-posed launch. The current device is the scene's; `stream` is a hipStream_t.
+int pose_launch_accum(rt_accum* a, const SceneD& sd, const ParamsD& P, unsigned blocks, void* stream);
+int pose_launch_list(rt_accum* a, const SceneD& sd, const ParamsD& P, const int32_t* list, size_t nlist, unsigned blocks,
+                     void* stream);
 
 }  // namespace rt

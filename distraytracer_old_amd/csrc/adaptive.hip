@@ -22,6 +22,7 @@ using namespace rt;
 
 namespace {
 
+// the kernels without a camera pose; an accumulator that has one launches pose.hip's (pose_launch_list)
 typedef void (*ListFn)(SceneD, ParamsD, const int32_t*, size_t, int32_t*, double*, double*);
 struct ListVariant {
   uint32_t mask;
@@ -80,6 +81,7 @@ int launch_list(rt_accum* a, const ParamsD& P, const int32_t* list, int64_t nlis
   int rc = perlin_ready(s->device);
   if (rc != RT_OK) return rc;
   const SceneD sd = render_scene_view(s, a->rp.flags & RT_RENDER_NOCULL);
+  if (a->has_pose) return pose_launch_list(a, sd, P, list, (size_t)nlist, (unsigned)blocks, st);
   const ListVariant& v = variant_for(kListVariants, render_variant_mask(s, a->rp.flags));
   hipLaunchKernelGGL(v.fn[a->sq ? 1 : 0], dim3((unsigned)blocks), dim3(64), dv::LDS_RENDER_BYTES, st, sd, P, list, (size_t)nlist, a->cnt,
                      a->sum, a->sq);

@@ -62,6 +62,7 @@ __global__ void __launch_bounds__(64) select_ballot_kernel(int W, int H, int til
   }
 }
 
+#ifndef RT_POSE_TU  // the kernels defined outright: adaptive.hip only (pose.hip instantiates the posed accum_list_kernel)
 // Step 2: the exclusive scan of the tile counts in place, c[ntiles] = the total. One block: every thread
 // sums a contiguous run of counts, the 256 partial sums are scanned in LDS, then every thread writes its
 // run's prefixes. No atomics: the list's order does not depend on scheduling.
@@ -100,6 +101,7 @@ __global__ void __launch_bounds__(64) select_scatter_kernel(int W, int H, int ti
   const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
   list[(size_t)toff[tile] + below] = (int32_t)sel_pixel(lane, tile, tilesX, W, H);
 }
+#endif  // RT_POSE_TU
 
 // accum_kernel over a list: one launch shades samples [cnt[p], cnt[p] + P.spp) of every listed pixel p, adds
 // them to the carried sums by accum_kernel's rules, and sets cnt[p] += P.spp.
@@ -115,10 +117,13 @@ __global__ void __launch_bounds__(64) select_scatter_kernel(int W, int H, int ti
 // written once, by the pixel's first lane after the last barrier, so every such read sees the count the
 // launch started with. A slot past the list's end and a tail sample lane stay out of trace_sample and reach
 // every barrier (the loop bounds are wave-uniform).
-template <uint32_t F, bool MOM>
+//
+// POSE and the last argument: as accum_kernel's.
+template <uint32_t F, bool MOM, bool POSE = false, class... M>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RT_RENDER_WAVES)))
 accum_list_kernel(SceneD S, ParamsD P, const int32_t* __restrict__ list, size_t nlist, int32_t* cnt, double* __restrict__ sum,
-                  double* __restrict__ sq) {
+                  double* __restrict__ sq, M... pose) {
+  RT_POSE_PACK_CHECK(POSE, M);
   constexpr bool FLAG = (F & FT_CAMX) != 0;
   double* cbuf = rt_lds;  // 64 x 4 doubles (colour, traced)
   const int lane = threadIdx.x;
@@ -153,6 +158,7 @@ accum_list_kernel(SceneD S, ParamsD P, const int32_t* __restrict__ list, size_t 
         V o, d;
         traced = camera_ray<F>(S, P, row, col, s, true, o, d);
         if (traced) {
+          pose_ray(o, d, pose...);
           k.pixel = (uint64_t)p;
           k.sample = (uint32_t)s;
           Counters ct;
@@ -219,6 +225,7 @@ accum_list_kernel(SceneD S, ParamsD P, const int32_t* __restrict__ list, size_t 
   }
 }
 
+#ifndef RT_POSE_TU
 // resolve_kernel with a sample count per pixel; a pixel without samples is black
 __global__ void __launch_bounds__(256) resolve_counts_kernel(const double* __restrict__ sum, const int32_t* __restrict__ cnt,
                                                              int64_t npix, float* __restrict__ rgb, int32_t* __restrict__ argb) {
@@ -249,6 +256,7 @@ __global__ void __launch_bounds__(256) error_counts_kernel(const double* __restr
   const int n = cnt[o];
   err[o] = n < 2 ? __builtin_inff() : pixel_error(sum, sq, o, n);
 }
+#endif  // RT_POSE_TU
 
 }  // namespace dv
 }  // namespace rt

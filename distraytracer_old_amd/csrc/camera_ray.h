@@ -80,5 +80,23 @@ __device__ __forceinline__ bool camera_ray(const SceneD& S, const ParamsD& P, in
   return traced;
 }
 
+// A camera pose applied to the ray camera_ray returned: o as a point, d as a vector (still not normalised),
+// by trace_device.h's xpt / xvec operation for operation -- per row a = 0.0, then a += m * x, y, z in turn
+// and a += m3 * 1.0 (point) or m3 * 0.0 (vector), every step rounded (the units are built
+// -ffp-contract=off). xpt and xvec read rows 0 .. 2 of a matrix only, which is what PoseD holds. The
+// matrix is a kernel argument and so wave-uniform: the multiplies take it from scalar registers
+// (DESIGN.md section 18 says where it waits between the rounds of a sample loop).
+__device__ __forceinline__ void pose_ray(V& o, V& d, const PoseD& M) {
+  o = xpt(M.m, o);
+  d = xvec(M.m, d);
+}
+// a kernel instantiated without a pose (its argument pack is empty): the ray as it is
+__device__ __forceinline__ void pose_ray(V&, V&) {}
+// The posed kernels are the un-posed ones with `bool POSE = false, class... M` behind their template
+// parameters and `M... pose` behind their arguments: POSE instantiations take one PoseD there, the others
+// nothing, so that an un-posed kernel keeps the argument list, and with it the code, it had before.
+#define RT_POSE_PACK_CHECK(POSE, M) \
+  static_assert(sizeof...(M) == ((POSE) ? 1 : 0), "a posed kernel takes one PoseD last, an un-posed one nothing")
+
 }  // namespace dv
 }  // namespace rt

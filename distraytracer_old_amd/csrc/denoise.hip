@@ -30,6 +30,9 @@ struct rt_denoise {
   int32_t* oargb;     // device [W * H]
   int32_t final_;     // the buffer that holds the last run's planes, -1 before any run
   void* last;         // hipStream_t of the last run
+  rt_ray* srays;      // device [W * H] and
+  rt_hit* shits;      // device [W * H]: the guide build's staging, kept from the first rt_denoise_rebuild on
+  uint64_t pose_gen;  // the accumulator's pose_gen the guides were traced under (rt_accum_set_camera moves it on)
 };
 
 // tests/test_denoise_abi.py points a host-made denoiser at a host-made accumulator through this field
@@ -47,18 +50,26 @@ void free_buffers(rt_denoise* d) {
   (void)hipFree(d->buf[1]);
   (void)hipFree(d->orgb);
   (void)hipFree(d->oargb);
+  (void)hipFree(d->srays);
+  (void)hipFree(d->shits);
 }
 
-// Traces the frame's centre rays and packs the guides, on st and waited for. The ray and hit staging
-// (56 + 80 bytes per pixel) lives only for the duration of the build.
-int build_guides(rt_denoise* d, hipStream_t st, const std::string& w) {
+// Traces the frame's centre rays, under the accumulator's camera pose if it has one, and packs the guides, on
+// st and waited for. The ray and hit staging
+// (56 + 80 bytes per pixel) lives only for the duration of the build, unless `keep`: then the denoiser's own
+// is used, allocated here the first time, so that a host that moves the camera every frame pays for it once.
+int build_guides(rt_denoise* d, hipStream_t st, const std::string& w, bool keep) {
   rt_accum* a = d->a;
   rt_scene* s = a->scene;
   const int64_t n = pixels(d);
-  rt_ray* rays = nullptr;
-  rt_hit* hits = nullptr;
-  hipError_t e = hipMalloc(&rays, (size_t)n * sizeof(rt_ray));
-  if (e == hipSuccess) e = hipMalloc(&hits, (size_t)n * sizeof(rt_hit));
+  rt_ray* rays = d->srays;
+  rt_hit* hits = d->shits;
+  hipError_t e = rays ? hipSuccess : hipMalloc(&rays, (size_t)n * sizeof(rt_ray));
+  if (e == hipSuccess && !hits) e = hipMalloc(&hits, (size_t)n * sizeof(rt_hit));
+  if (keep) {
+    d->srays = rays;
+    d->shits = hits;
+  }
   int rc = e == hipSuccess ? RT_OK : set_error(RT_E_HIP, w + ": " + hipGetErrorString(e));
   if (rc == RT_OK) {
     rt_render_params q = a->rp;
@@ -68,7 +79,7 @@ int build_guides(rt_denoise* d, hipStream_t st, const std::string& w) {
     tp.seed = a->rp.seed;
     tp.first_key = 0;
     tp.flags = trace_flags_of(a->rp.flags);
-    rc = rt_camera_rays_device(s, &q, 0, rays, st);
+    rc = rt_camera_rays_pose_device(s, &q, 0, a->has_pose ? a->pose : nullptr, rays, st);
     if (rc == RT_OK) rc = rt_trace_rays_device(s, &tp, rays, n, hits, nullptr, st);
     if (rc != RT_OK) rc = set_error(rc, w + ": " + rt_last_error());
   }
@@ -78,9 +89,10 @@ int build_guides(rt_denoise* d, hipStream_t st, const std::string& w) {
     if (e != hipSuccess) rc = set_error(RT_E_HIP, w + ": " + hipGetErrorString(e));
   }
   const hipError_t se = hipStreamSynchronize(st);
-  (void)hipFree(rays);
-  (void)hipFree(hits);
+  if (!d->srays) (void)hipFree(rays);
+  if (!d->shits) (void)hipFree(hits);
   if (rc == RT_OK && se != hipSuccess) rc = set_error(RT_E_HIP, w + ": " + hipGetErrorString(se));
+  if (rc == RT_OK) d->pose_gen = a->pose_gen;
   return rc;
 }
 
@@ -94,6 +106,8 @@ int check_run(const std::string& w, const rt_denoise* d, const rt_denoise_params
   const rt_accum* a = d->a;
   const int64_t any = (a->flags & RT_ACCUM_COUNTS) ? a->bound : a->done;
   if (any < 1) return set_error(RT_E_INVALID, w + ": no samples accumulated yet");
+  if (d->pose_gen != a->pose_gen)
+    return set_error(RT_E_INVALID, w + ": the guides are of another camera (rt_accum_set_camera was called since: rt_denoise_rebuild)");
   return RT_OK;
 }
 
@@ -160,7 +174,7 @@ int rt_denoise_create(rt_accum* a, rt_denoise** out) {
   if (e == hipSuccess) e = hipMalloc(&d->orgb, n * 3 * sizeof(float));
   if (e == hipSuccess) e = hipMalloc(&d->oargb, n * sizeof(int32_t));
   int rc = e == hipSuccess ? RT_OK : set_error(RT_E_HIP, w + ": " + hipGetErrorString(e));
-  if (rc == RT_OK) rc = build_guides(d, (hipStream_t)a->scene->stream, w);
+  if (rc == RT_OK) rc = build_guides(d, (hipStream_t)a->scene->stream, w, false);
   if (rc != RT_OK) {
     free_buffers(d);
     delete d;
@@ -168,6 +182,18 @@ int rt_denoise_create(rt_accum* a, rt_denoise** out) {
   }
   *out = d;
   return RT_OK;
+}
+
+int rt_denoise_rebuild(rt_denoise* d) {
+  const std::string w("rt_denoise_rebuild");
+  if (!d) return set_error(RT_E_INVALID, w + ": null denoiser");
+  rt_accum* a = d->a;
+  DeviceGuard dg;
+  HIPCHK(hipSetDevice(a->scene->device));
+  HIPCHK(hipStreamSynchronize((hipStream_t)a->last));  // as creation: the trace is the scene's one in-flight render
+  HIPCHK(hipStreamSynchronize((hipStream_t)d->last));  // a run in flight reads the guides
+  d->final_ = -1;  // the planes are of the old guides
+  return build_guides(d, (hipStream_t)a->scene->stream, w, true);
 }
 
 int rt_denoise_guides(rt_denoise* d, float* normal, float* pos, float* depth, int32_t* material) {

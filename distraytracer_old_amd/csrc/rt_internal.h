@@ -116,6 +116,10 @@ void sort_free(rt_scene* s);
 // reaches the noise textures uploads into its own c_perm / c_grad3 (launch_common.h perlin_ready).
 int trace_stage(rt_scene* s, int64_t n, void** stream);
 void perlin_tables(const int** perm, const int** grad3);
+// pose.hip: why `pose` (16 doubles, row-major) is not a valid camera pose by rt_camera_pose_check's rule,
+// nullptr for a valid one; and the twelve entries of a valid one the posed kernels take
+const char* pose_invalid(const double* pose);
+PoseD pose_args(const double* pose);
 // group.hip: the deterministic rank plan (rt_rank_plan)
 void plan_ranks(const uint32_t* cost, int n, int world, double heavy, int slots, int32_t* owner, int32_t* order,
                 const double* weight = nullptr);

@@ -235,4 +235,11 @@ struct ParamsD {
   double orthPerRow, orthPerCol;              // ortho
 };
 
+// A camera pose (rt_camera_rays_pose, rt_accum_set_camera): rows 0 .. 2 of the row-major camera-to-world
+// matrix, the twelve entries xpt / xvec read. A kernel argument of its own, by value, of the posed kernels
+// alone: SceneD and ParamsD, which every kernel takes, stay as they are.
+struct PoseD {
+  double m[12];
+};
+
 }  // namespace rt

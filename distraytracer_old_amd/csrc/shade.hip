@@ -13,6 +13,7 @@
 // as render_minreg.hip: trace.hip alone holds the kernels trace_kernels.h defines outright
 #define RT_MINREG_TU
 #include "rt_internal.h"
+#include "comm.h"
 #include "shade_kernels.h"
 #define RT_UNIT_SHADES  // the kernels reach the noise textures: this unit uploads its own Perlin tables
 #include "launch_common.h"
@@ -111,14 +112,50 @@ int camera_params(const char* who, rt_scene* s, const rt_render_params* p, int s
   return RT_OK;
 }
 
-int launch_camera(const rt_scene* s, const ParamsD& P, int sample, int64_t first, int64_t count, rt_ray* d_rays, hipStream_t st) {
-  hipLaunchKernelGGL(dv::camera_rays_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, s->dev, P, sample, first,
-                     count, d_rays);
+// pose: the rows of a valid camera pose, or nullptr for the camera as it is (the kernel without one)
+int launch_camera(const rt_scene* s, const ParamsD& P, int sample, int64_t first, int64_t count, rt_ray* d_rays, const double* pose,
+                  hipStream_t st) {
+  const dim3 grid((unsigned)((count + 255) / 256));
+  if (pose) {
+    hipLaunchKernelGGL(dv::camera_rays_kernel<true>, grid, dim3(256), 0, st, s->dev, P, sample, first, count, d_rays, pose_args(pose));
+  } else {
+    hipLaunchKernelGGL(dv::camera_rays_kernel<false>, grid, dim3(256), 0, st, s->dev, P, sample, first, count, d_rays);
+  }
   HIPCHK(hipGetLastError());
   return RT_OK;
 }
 
+// a posed camera entry's pose, checked before the scene is read
+int check_pose(const char* who, const double* pose) {
+  const char* why = pose_invalid(pose);
+  return why ? set_error(RT_E_INVALID, std::string(who) + ": " + why) : RT_OK;
+}
+
 constexpr int64_t CAMERA_SLICE = (int64_t)1 << 30;  // rays per launch: 2^22 blocks
+
+// the frame's rays into a device buffer, asynchronous on st
+int camera_device(rt_scene* s, const ParamsD& P, int sample, const double* pose, rt_ray* d_rays, hipStream_t st) {
+  HIPCHK(hipSetDevice(s->device));
+  const int64_t n = (int64_t)P.W * P.H;
+  for (int64_t at = 0; at < n; at += CAMERA_SLICE) {
+    const int rc = launch_camera(s, P, sample, at, std::min(CAMERA_SLICE, n - at), d_rays + at, pose, st);
+    if (rc != RT_OK) return rc;
+  }
+  return RT_OK;
+}
+
+// the frame's rays into a host buffer through the scene's staging, blocking
+int camera_host(const char* who, rt_scene* s, const ParamsD& P, int sample, const double* pose, rt_ray* rays) {
+  const int64_t n = (int64_t)P.W * P.H;
+  return staged_chunks(
+      who, s, n,
+      [&](const Staging& g, int64_t at, size_t m, hipStream_t st) {
+        Enqueued q = {launch_camera(s, P, sample, at, (int64_t)m, g.dev.rays, pose, st), hipSuccess};
+        if (q.rc == RT_OK) q.e = hipMemcpyAsync(g.pin.rays, g.dev.rays, m * sizeof(rt_ray), hipMemcpyDeviceToHost, st);
+        return q;
+      },
+      [&](const Staging& g, int64_t at, size_t m) { std::memcpy(rays + at, g.pin.rays, m * sizeof(rt_ray)); });
+}
 
 }  // namespace
 
@@ -154,28 +191,35 @@ int rt_shade_rays(rt_scene* s, const rt_shade_params* p, const rt_ray* rays, int
 
 int rt_camera_rays_device(rt_scene* s, const rt_render_params* p, int sample, rt_ray* d_rays, void* hip_stream) {
   ParamsD P;
-  int rc = camera_params("rt_camera_rays_device", s, p, sample, d_rays, P);
+  const int rc = camera_params("rt_camera_rays_device", s, p, sample, d_rays, P);
   if (rc) return rc;
-  HIPCHK(hipSetDevice(s->device));
-  const int64_t n = (int64_t)P.W * P.H;
-  for (int64_t at = 0; at < n; at += CAMERA_SLICE)
-    if ((rc = launch_camera(s, P, sample, at, std::min(CAMERA_SLICE, n - at), d_rays + at, (hipStream_t)hip_stream)) != RT_OK) return rc;
-  return RT_OK;
+  return camera_device(s, P, sample, nullptr, d_rays, (hipStream_t)hip_stream);
 }
 
 int rt_camera_rays(rt_scene* s, const rt_render_params* p, int sample, rt_ray* rays) {
   ParamsD P;
-  int rc = camera_params("rt_camera_rays", s, p, sample, rays, P);
+  const int rc = camera_params("rt_camera_rays", s, p, sample, rays, P);
   if (rc) return rc;
-  const int64_t n = (int64_t)P.W * P.H;
-  return staged_chunks(
-      "rt_camera_rays", s, n,
-      [&](const Staging& g, int64_t at, size_t m, hipStream_t st) {
-        Enqueued q = {launch_camera(s, P, sample, at, (int64_t)m, g.dev.rays, st), hipSuccess};
-        if (q.rc == RT_OK) q.e = hipMemcpyAsync(g.pin.rays, g.dev.rays, m * sizeof(rt_ray), hipMemcpyDeviceToHost, st);
-        return q;
-      },
-      [&](const Staging& g, int64_t at, size_t m) { std::memcpy(rays + at, g.pin.rays, m * sizeof(rt_ray)); });
+  return camera_host("rt_camera_rays", s, P, sample, nullptr, rays);
+}
+
+int rt_camera_rays_pose_device(rt_scene* s, const rt_render_params* p, int sample, const double* pose, rt_ray* d_rays,
+                               void* hip_stream) {
+  if (!pose) return rt_camera_rays_device(s, p, sample, d_rays, hip_stream);
+  ParamsD P;
+  int rc = check_pose("rt_camera_rays_pose_device", pose);
+  if (rc || (rc = camera_params("rt_camera_rays_pose_device", s, p, sample, d_rays, P)) != RT_OK) return rc;
+  DeviceGuard dg;
+  return camera_device(s, P, sample, pose, d_rays, (hipStream_t)hip_stream);
+}
+
+int rt_camera_rays_pose(rt_scene* s, const rt_render_params* p, int sample, const double* pose, rt_ray* rays) {
+  if (!pose) return rt_camera_rays(s, p, sample, rays);
+  ParamsD P;
+  int rc = check_pose("rt_camera_rays_pose", pose);
+  if (rc || (rc = camera_params("rt_camera_rays_pose", s, p, sample, rays, P)) != RT_OK) return rc;
+  DeviceGuard dg;
+  return camera_host("rt_camera_rays_pose", s, P, sample, pose, rays);
 }
 
 }  // extern "C"

@@ -65,15 +65,19 @@ shade_kernel_idx(SceneD S, uint64_t seed, uint64_t firstKey, uint32_t sample, co
 
 // camera_ray (camera_ray.h) for sample s of pixel first + i of a whole-frame layout (ray index = pixel key), into
 // rays[i], tmax = +Inf: jittered when the frame has two samples or more. An untraced fisheye sample gets
-// d = 0: every query rejects it.
+// d = 0: every query rejects it. POSE: the ray is posed by the PoseD behind the arguments (camera_ray.h
+// pose_ray) before that; the origin of an untraced sample is posed too, its d stays +0.
+template <bool POSE = false, class... M>
 __global__ void __launch_bounds__(256) camera_rays_kernel(SceneD S, ParamsD P, int s, int64_t first, int64_t count,
-                                                          rt_ray* __restrict__ rays) {
+                                                          rt_ray* __restrict__ rays, M... pose) {
+  RT_POSE_PACK_CHECK(POSE, M);
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= count) return;
   const int64_t px = first + i;
   const int row = (int)(px / P.W), col = (int)(px % P.W);
   V o, d;
   const bool traced = camera_ray<(uint32_t)FT_ALL>(S, P, row, col, s, P.spp != 1, o, d);
+  pose_ray(o, d, pose...);
   if (!traced) d = mk(0, 0, 0);
   double* w = (double*)(rays + i);
   w[0] = o.x; w[1] = o.y; w[2] = o.z;

@@ -74,7 +74,10 @@ EXPORTS = ["rt_abi_version", "rt_build_id", "rt_last_error", "rt_device_count", 
            "rt_accum_add_selected", "rt_accum_counts", "rt_accum_counts_device", "rt_accum_restore_counts",
            # added to ABI 7: the variance-guided a-trous denoiser of an accumulated frame
            "rt_denoise_defaults", "rt_denoise_create", "rt_denoise_guides", "rt_denoise_run", "rt_denoise_run_device",
-           "rt_denoise_planes", "rt_denoise_destroy"]
+           "rt_denoise_planes", "rt_denoise_destroy",
+           # added to ABI 7: the camera pose (the eye moved over the scene as uploaded)
+           "rt_camera_pose_check", "rt_camera_look_at", "rt_camera_rays_pose", "rt_camera_rays_pose_device",
+           "rt_accum_set_camera", "rt_accum_camera", "rt_denoise_rebuild"]
 
 _lib = None
 
@@ -227,6 +230,14 @@ def lib():
             L.rt_denoise_planes.argtypes = [vp, vp, vp]
             L.rt_denoise_destroy.argtypes = [vp]
             L.rt_denoise_destroy.restype = None
+        if hasattr(L, "rt_accum_set_camera"):  # added to ABI 7
+            L.rt_camera_pose_check.argtypes = [vp]
+            L.rt_camera_look_at.argtypes = [vp, vp, vp, vp]
+            L.rt_camera_rays_pose.argtypes = [vp, vp, ctypes.c_int, vp, vp]
+            L.rt_camera_rays_pose_device.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp]
+            L.rt_accum_set_camera.argtypes = [vp, vp]
+            L.rt_accum_camera.argtypes = [vp, vp, vp]
+            L.rt_denoise_rebuild.argtypes = [vp]
         _lib = L
     return _lib
 
@@ -253,6 +264,32 @@ def png_name(save_name: str) -> str:
 def _check(rc: int, what: str):
     if rc != 0:
         raise RTError(f"{what} failed ({rc}): {lib().rt_last_error().decode()}")
+
+
+def _pose(pose):
+    """A pose argument as a contiguous float64 [16] (None stays None: no pose)."""
+    if pose is None:
+        return None
+    m = np.ascontiguousarray(pose, dtype=np.float64)
+    if m.size != 16:
+        raise ValueError("a pose is a 4 x 4 matrix, row-major, camera -> world")
+    return m.reshape(16)
+
+
+def look_at(eye, target, up=(0, 1, 0)) -> np.ndarray:
+    """The camera pose (float64 [4, 4], camera -> world) of an eye at `eye` that looks at `target` with `up`
+    upwards (rt_camera_look_at)."""
+    e, t, u = (np.ascontiguousarray(v, dtype=np.float64).reshape(3) for v in (eye, target, up))
+    m = np.zeros(16, dtype=np.float64)
+    _check(lib().rt_camera_look_at(e.ctypes.data, t.ctypes.data, u.ctypes.data, m.ctypes.data), "rt_camera_look_at")
+    return m.reshape(4, 4)
+
+
+def pose_check(pose) -> None:
+    """Raises RTError unless `pose` is a valid camera pose: finite, last row 0 0 0 1, a proper rotation and a
+    translation (rt_camera_pose_check)."""
+    m = _pose(pose)
+    _check(lib().rt_camera_pose_check(None if m is None else m.ctypes.data), "rt_camera_pose_check")
 
 
 def math_eval(x, device: int = 0) -> np.ndarray:
@@ -862,27 +899,38 @@ class Scene:
                                           ctypes.c_void_p(rgb_ptr or None), ctypes.c_void_p(status_ptr or None),
                                           ctypes.c_void_p(stream or None)), "rt_shade_rays_device")
 
-    def camera_rays(self, W, H, spp=0, seed=0x5EED0001, sample=0) -> np.ndarray:
+    def camera_rays(self, W, H, spp=0, seed=0x5EED0001, sample=0, pose=None) -> np.ndarray:
         """The rays a W x H render at spp shoots for sample `sample` of every pixel -> desc.RAY_DTYPE [H * W],
-        row-major: index = pixel key (rt_camera_rays). An untraced fisheye sample has d = 0."""
+        row-major: index = pixel key (rt_camera_rays). An untraced fisheye sample has d = 0. pose: a camera
+        pose (look_at) applied to every ray (rt_camera_rays_pose)."""
         from .desc import RAY_DTYPE
 
         p = params(W, H, spp, seed)
         r = np.zeros(W * H, dtype=RAY_DTYPE)
-        _check(lib().rt_camera_rays(self._h, ctypes.byref(p), sample, r.ctypes.data), "rt_camera_rays")
+        if pose is None:
+            _check(lib().rt_camera_rays(self._h, ctypes.byref(p), sample, r.ctypes.data), "rt_camera_rays")
+        else:
+            _check(lib().rt_camera_rays_pose(self._h, ctypes.byref(p), sample, _pose(pose).ctypes.data, r.ctypes.data),
+                   "rt_camera_rays_pose")
         return r
 
-    def camera_rays_device(self, p: RenderParams, rays_ptr: int, sample: int = 0, stream: int = 0):
+    def camera_rays_device(self, p: RenderParams, rays_ptr: int, sample: int = 0, stream: int = 0, pose=None):
         """Asynchronous rt_camera_rays into a device rt_ray [height * width] buffer on a HIP stream
-        (rt_camera_rays_device)."""
-        _check(lib().rt_camera_rays_device(self._h, ctypes.byref(p), sample, ctypes.c_void_p(rays_ptr or None),
-                                           ctypes.c_void_p(stream or None)), "rt_camera_rays_device")
+        (rt_camera_rays_device; with a pose rt_camera_rays_pose_device)."""
+        if pose is None:
+            _check(lib().rt_camera_rays_device(self._h, ctypes.byref(p), sample, ctypes.c_void_p(rays_ptr or None),
+                                               ctypes.c_void_p(stream or None)), "rt_camera_rays_device")
+        else:
+            _check(lib().rt_camera_rays_pose_device(self._h, ctypes.byref(p), sample, _pose(pose).ctypes.data,
+                                                    ctypes.c_void_p(rays_ptr or None), ctypes.c_void_p(stream or None)),
+                   "rt_camera_rays_pose_device")
 
-    def accumulator(self, W, H, seed=0x5EED0001, flags=0, moments=False, counts=False) -> "Accumulator":
+    def accumulator(self, W, H, seed=0x5EED0001, flags=0, moments=False, counts=False, pose=None) -> "Accumulator":
         """A W x H frame that converges in place (rt_accum_create): samples are added in chunks and the frame
         so far resolved between them. flags: RENDER_GENERIC / RENDER_NOCULL; moments=True also keeps the sums
-        of squares the error map needs, counts=True a sample count per pixel (select_* / add_selected)."""
-        return Accumulator(self, W, H, seed, flags, moments, counts)
+        of squares the error map needs, counts=True a sample count per pixel (select_* / add_selected); pose: the
+        camera pose it starts with (Accumulator.set_camera)."""
+        return Accumulator(self, W, H, seed, flags, moments, counts, pose)
 
     def render_pixels_device(self, p: RenderParams, pixels: np.ndarray, rgb_ptr: int, argb_ptr: int, stream: int = 0):
         """Asynchronous one-sample-per-wave render of the listed pixels (host int32 list) into whole-frame buffers."""
@@ -928,7 +976,7 @@ class Accumulator:
     resolve() is Scene.render(spp=N) bit for bit, however the samples were cut into chunks. Holds a reference
     to its scene (an accumulator must be closed before its scene)."""
 
-    def __init__(self, scene: Scene, W, H, seed=0x5EED0001, flags=0, moments=False, counts=False):
+    def __init__(self, scene: Scene, W, H, seed=0x5EED0001, flags=0, moments=False, counts=False, pose=None):
         self._h, self._nsel = None, 0
         self.scene, self.W, self.H, self.moments, self.has_counts = scene, W, H, bool(moments), bool(counts)
         p = params(W, H, 0, seed, flags=flags)
@@ -936,6 +984,24 @@ class Accumulator:
         _check(lib().rt_accum_create(scene._h, ctypes.byref(p), (ACCUM_MOMENTS if moments else 0) | (ACCUM_COUNTS if counts else 0),
                                      ctypes.byref(h)), "rt_accum_create")
         self._h = h
+        if pose is not None:
+            self.set_camera(pose)
+
+    def set_camera(self, pose):
+        """Look through another camera pose (look_at; None: the scene's own camera again) and start the frame
+        over: everything reset() does, and every sample from now on is of the posed rays. The scene and its
+        photon map are not touched (rt_accum_set_camera)."""
+        m = _pose(pose)
+        _check(lib().rt_accum_set_camera(self._h, None if m is None else m.ctypes.data), "rt_accum_set_camera")
+        self._nsel = 0
+
+    @property
+    def camera(self):
+        """The pose set_camera gave (float64 [4, 4]), None when there is none (rt_accum_camera)."""
+        m = np.zeros(16, dtype=np.float64)
+        on = ctypes.c_int(0)
+        _check(lib().rt_accum_camera(self._h, m.ctypes.data, ctypes.byref(on)), "rt_accum_camera")
+        return m.reshape(4, 4) if on.value else None
 
     def add(self, count: int, stream: int = 0):
         """Shade the next `count` samples of every pixel; asynchronous on `stream` (0: the scene's own)."""
@@ -1093,6 +1159,11 @@ class Denoiser:
         h = ctypes.c_void_p()
         _check(lib().rt_denoise_create(accum._h, ctypes.byref(h)), "rt_denoise_create")
         self._h = h
+
+    def rebuild(self):
+        """Trace the guides again for the accumulator's current camera pose, into the same buffers: what a run
+        needs after Accumulator.set_camera (rt_denoise_rebuild). Blocks."""
+        _check(lib().rt_denoise_rebuild(self._h), "rt_denoise_rebuild")
 
     def guides(self) -> dict:
         """The guides of the frame's centre rays: normal float32 [H, W, 3], pos float32 [H, W, 3], depth float32

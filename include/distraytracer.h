@@ -799,6 +799,70 @@ int rt_denoise_run_device(rt_denoise* d, const rt_denoise_params* p, float* d_rg
 int rt_denoise_planes(rt_denoise* d, double* colour, double* variance);
 void rt_denoise_destroy(rt_denoise* d);
 
+/* ---- Camera pose (added to ABI 7; probe the seven entries with dlsym) -----------------------------------
+   The eye moved over the scene as uploaded: no new scene, no BVH rebuild, no photon pre-pass (the photon map
+   does not depend on the eye). Without a pose the camera sits at the origin and looks down -z with +y up, as
+   the reference's cameras do. RT_ABI_VERSION stays 7.
+
+   A pose is double pose[16], row-major like every CTM here: camera space -> world space. A NULL pose means
+   "no pose" everywhere and takes the code path, and gives the bytes, of the entry without one. A ray (o, d) as
+   the camera code makes it (rt_camera_rays) becomes o' = M o as a point and d' = M d as a vector, per row r
+       a = 0.0;  a += m[r][0] * x;  a += m[r][1] * y;  a += m[r][2] * z;  a += m[r][3] * 1.0   (point)
+                                                                         a += m[r][3] * 0.0   (vector)
+   every product and every sum rounded on its own, never fused: a restatement of these adds and multiplies
+   over the un-posed rays gives the posed rays' bytes. All five camera paths alike (field of view at 1 spp
+   and jittered, depth of field, fisheye, orthographic). d is transformed as the camera code hands it over,
+   not normalised (the ray constructor does that afterwards, as without a pose); a pixel's RNG key stays
+   row * width + col; a fisheye sample outside the image circle keeps d = (+0, +0, +0), has its origin posed
+   and is not traced. The identity is NOT promised to equal "no pose" bit for bit: 0.0 + (-0.0) is +0.0, so
+   a zero component of d can change its sign.
+
+   A valid pose: all 16 entries finite; the last row exactly 0 0 0 1; the upper 3 x 3 R with
+   |R R^T - I| <= 1e-9 per entry and det R > 0, both in plain doubles on the host -- a rigid motion, no scale,
+   shear or reflection. It maps a non-zero finite d to a non-zero finite d', so a posed kernel meets no ray an
+   un-posed one could not. Anything else is RT_E_INVALID.
+
+   rt_camera_pose_check (host only): RT_OK, or RT_E_INVALID with a message that names the failed condition.
+   rt_camera_look_at (host only): f = (target - eye) / |target - eye|, r = cross(f, up) / |cross(f, up)|,
+   u = cross(r, f), with |v| = sqrt((x * x + y * y) + z * z), every component divided by it, and cross(a, b) =
+   (a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x). The rows of pose are
+   [r.x u.x -f.x eye.x], [r.y u.y -f.y eye.y], [r.z u.z -f.z eye.z], [0 0 0 1]. RT_E_INVALID when a norm is
+   zero or not finite (eye == target, up parallel to the view, a NaN), or when up is so nearly parallel that
+   the result would not pass rt_camera_pose_check: what comes out always passes it.
+
+   rt_camera_rays_pose / rt_camera_rays_pose_device: rt_camera_rays / rt_camera_rays_device with the pose
+   applied; with pose == NULL exactly those.
+
+   rt_accum_set_camera sets the accumulator's pose (NULL clears it). It does everything rt_accum_reset does:
+   waits for the last add, zeroes the sums, squares and counts, done = 0, and a selection becomes invalid.
+   The scene, its BVH and its photon map are not touched. From then on every ray the accumulator makes is
+   posed -- rt_accum_add, rt_accum_add_selected, rt_accum_add with mixed counts: sample s of a pixel is the ray
+   rt_camera_rays_pose emits for sample = s, spp >= 2, shaded under the unchanged key. The sums, the chunk
+   invariance and the resolve, error and select rules are the ones above. The equality with rt_render(spp = n)
+   holds only without a pose (rt_render has none); with one the yardstick is the fold of rt_shade_rays over
+   the posed camera rays. rt_accum_restore* keep the pose and a checkpoint does not hold it: a checkpointing
+   host stores the pose itself. rt_accum_camera reads it back: the pose and *is_set = 1, or the identity and
+   *is_set = 0 when none is set.
+
+   Denoiser: rt_denoise_create traces its guides from rt_camera_rays_pose_device with the accumulator's pose
+   (the depth is measured from the posed origin) and remembers which pose they are of. After a later
+   rt_accum_set_camera, rt_denoise_run* is RT_E_INVALID ("the guides are of another camera") until
+   rt_denoise_rebuild, which re-traces the guides into the existing buffers for the current pose and blocks,
+   as creation does; rt_denoise_planes is RT_E_INVALID again until the next run. The first rebuild allocates
+   the build's ray and hit staging (136 bytes per pixel), which the denoiser then keeps: later ones allocate
+   nothing.
+
+   Bad arguments are RT_E_INVALID with a message that starts with the entry's name, before the scene or a
+   device is touched; every entry restores the caller's current device. */
+int rt_camera_pose_check(const double* pose);
+int rt_camera_look_at(const double* eye, const double* target, const double* up, double* pose);
+int rt_camera_rays_pose(rt_scene* scene, const rt_render_params* p, int sample, const double* pose, rt_ray* rays);
+int rt_camera_rays_pose_device(rt_scene* scene, const rt_render_params* p, int sample, const double* pose, rt_ray* d_rays,
+                               void* hip_stream);
+int rt_accum_set_camera(rt_accum* a, const double* pose);
+int rt_accum_camera(const rt_accum* a, double* pose, int* is_set);
+int rt_denoise_rebuild(rt_denoise* d);
+
 #ifdef __cplusplus
 }
 #endif

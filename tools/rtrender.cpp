@@ -4,7 +4,7 @@
 //
 //   rtrender <scene_dir> <file.cli> [-w W] [-h H] [-spp N] [-seed S] [-device D] [-o out.png]
 //            [-rgb out.f32] [-tex name=path.ppm]... [-time ITERS] [-nodir] [-budget MS] [-noise E [-max N]]
-//            [-denoise [LEVELS]]
+//            [-denoise [LEVELS]] [-eye X Y Z -at X Y Z [-up X Y Z]]
 //
 // -budget MS: the best frame MS milliseconds give, in place of -spp's fixed count -- samples are accumulated
 // (rt_accum_*) in chunks of 2, 2, 4, 8, ... doubling up to 64 until the wall time since the first chunk was
@@ -19,6 +19,12 @@
 // -denoise [LEVELS]: the written frame is the denoised one (rt_denoise_*, the defaults with LEVELS a-trous levels
 // if given) instead of the resolved one. With -budget and -noise the accumulator of that mode also keeps the
 // moments; with a plain -spp N (N >= 2) the N samples go through a moments accumulator in one add.
+//
+// -eye X Y Z -at X Y Z [-up X Y Z]: the frame as seen from the eye at X Y Z looking at the point -at, with -up
+// (default 0 1 0) upwards, over the scene as the .cli places it (rt_camera_look_at, rt_accum_set_camera). The frame
+// is rendered through an accumulator with that pose: it combines with -budget, -noise and -denoise as they are, and
+// a plain -spp N (N >= 1, required) adds the N samples in one add and writes the resolved frame. Without -eye every
+// path above and its output are as they were.
 //
 // Without -o the image goes where myScene.saveFile puts it (myScene.java:1185-1196): the
 // `write` name (rt_scene_save_name) inside the folder "pics.<yyyy.MM.dd.hh.mm>" the scene
@@ -103,7 +109,7 @@ int main(int argc, char** argv) {
   if (argc < 3) {
     std::fprintf(stderr, "usage: %s <scene_dir> <file.cli> [-w W] [-h H] [-spp N] [-seed S] [-device D] "
                          "[-o out.png] [-rgb out.f32] [-tex name=path.ppm]... [-time ITERS] [-nodir] [-budget MS] "
-                         "[-noise E [-max N]] [-denoise [LEVELS]]\n", argv[0]);
+                         "[-noise E [-max N]] [-denoise [LEVELS]] [-eye X Y Z -at X Y Z [-up X Y Z]]\n", argv[0]);
     return 2;
   }
   std::string dir = argv[1], cli = argv[2], out, rgbOut;
@@ -114,6 +120,8 @@ int main(int argc, char** argv) {
   int maxSamples = 1024;
   bool denoise = false;
   int denoiseLevels = -1;  // >= 0: that many levels instead of the default
+  bool haveEye = false, haveAt = false;
+  double eye[3] = {0, 0, 0}, at[3] = {0, 0, -1}, up[3] = {0, 1, 0};
   uint64_t seed = 0x5EED0001ull;
   std::vector<std::string> texNames, texPaths;
   for (int i = 3; i < argc; ++i) {
@@ -138,6 +146,9 @@ int main(int argc, char** argv) {
       denoise = true;
       if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') denoiseLevels = std::atoi(argv[++i]);
     }
+    else if (a == "-eye") { haveEye = true; for (double& v : eye) v = std::atof(next().c_str()); }
+    else if (a == "-at") { haveAt = true; for (double& v : at) v = std::atof(next().c_str()); }
+    else if (a == "-up") { for (double& v : up) v = std::atof(next().c_str()); }
     else if (a == "-tex") {
       std::string t = next();
       size_t eq = t.find('=');
@@ -146,6 +157,10 @@ int main(int argc, char** argv) {
       texPaths.push_back(t.substr(eq + 1));
     } else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
   }
+  double pose[16];
+  if (haveEye != haveAt) { std::fprintf(stderr, "-eye and -at go together\n"); return 2; }
+  if (haveEye && rt_camera_look_at(eye, at, up, pose)) { std::fprintf(stderr, "%s\n", rt_last_error()); return 2; }
+  if (haveEye && noise < 0 && budgetMs < 0 && spp < 1) { std::fprintf(stderr, "-eye expects -spp of at least 1, -budget or -noise\n"); return 2; }
   std::vector<std::vector<uint8_t>> texData(texNames.size());
   std::vector<rt_texture_desc> tex(texNames.size());
   std::vector<const char*> names(texNames.size());
@@ -190,6 +205,12 @@ int main(int argc, char** argv) {
     rt_denoise_destroy(dn);
     return r;
   };
+  // the accumulator of a mode, looking through -eye's pose if one was given
+  auto accumulator = [&](uint32_t flags, rt_accum** acc) -> int {
+    int r = rt_accum_create(s, &p, flags, acc);
+    if (r == 0 && haveEye) r = rt_accum_set_camera(*acc, pose);
+    return r;
+  };
   if (denoise && noise < 0 && budgetMs < 0 && spp < 2) {
     std::fprintf(stderr, "-denoise expects -spp of at least 2, -budget or -noise\n");
     rt_scene_destroy(s);
@@ -198,7 +219,7 @@ int main(int argc, char** argv) {
   if (noise >= 0) {
     if (maxSamples < 1) { std::fprintf(stderr, "-max expects at least 1\n"); rt_scene_destroy(s); return 2; }
     rt_accum* acc = nullptr;
-    rc = rt_accum_create(s, &p, RT_ACCUM_MOMENTS | RT_ACCUM_COUNTS, &acc);
+    rc = accumulator(RT_ACCUM_MOMENTS | RT_ACCUM_COUNTS, &acc);
     int top = maxSamples < 4 ? maxSamples : 4;  // no pixel has more samples than this
     if (rc == 0) rc = rt_accum_add(acc, top, nullptr);
     for (int chunk = 4; rc == 0; chunk = chunk < 64 ? chunk * 2 : 64) {
@@ -220,7 +241,7 @@ int main(int argc, char** argv) {
     std::printf("pixels %lld samples %lld max %d\n", (long long)W * H, total, most);
   } else if (budgetMs >= 0) {
     rt_accum* acc = nullptr;
-    rc = rt_accum_create(s, &p, denoise ? RT_ACCUM_MOMENTS : 0, &acc);
+    rc = accumulator(denoise ? RT_ACCUM_MOMENTS : 0, &acc);
     int64_t n = 0;
     const auto t0 = std::chrono::steady_clock::now();
     for (int chunk = 2, first = 1; rc == 0; first = 0) {
@@ -233,9 +254,9 @@ int main(int argc, char** argv) {
     rt_accum_destroy(acc);
     if (rc) { std::fprintf(stderr, "rt_accum: %d %s\n", rc, rt_last_error()); rt_scene_destroy(s); return 1; }
     std::printf("samples %lld\n", (long long)n);
-  } else if (denoise) {
+  } else if (denoise || haveEye) {
     rt_accum* acc = nullptr;
-    rc = rt_accum_create(s, &p, RT_ACCUM_MOMENTS, &acc);
+    rc = accumulator(denoise ? RT_ACCUM_MOMENTS : 0, &acc);
     if (rc == 0) rc = rt_accum_add(acc, spp, nullptr);
     if (rc == 0) rc = frame(acc);
     rt_accum_destroy(acc);
